@@ -1,8 +1,19 @@
 """Benchmark: HetroGIN training steps on MI355X (BASELINE.json metric), one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: build the graph and the model, W warm-up steps, the K timed steps,
+the ``--dump-outputs`` files if asked for, the result line.  Everything else this file measures — the CSR-build times,
+the untimed per-kernel probe pass (``roofline``, ``gemm*``), the sampler / decoder / real-loop / GAT extras, the cfg5
+twin, the N > 1 single-GPU reference and the CPU baseline — runs only with ``--full`` (their fields are null in a
+plain line); the ``--no-*`` switches then drop single parts of it as before.
+
+``--dump-outputs DIR`` writes what a caller of the timed step holds after the last timed step, as float32 ``.npy``
+files: ``loss.npy`` (the step's return value), ``param.<name>.npy`` (every model parameter after that step's Adam
+update) and ``grad.<name>.npy`` (its gradient, after the all-reduce at N > 1).  Graph, features, labels and initial
+weights are seeded, so two builds run with the same arguments are compared file by file.
 
 A step is one train.py iteration (train.py:31-44) on a resident synthetic hetero graph: zero_grad,
 forward through every relation of every layer (as PyG computes them), sqrt(MAPE), backward, the RCCL
@@ -23,10 +34,10 @@ fp32 — the graph the north star's >= 60 %-of-HBM aggregate target is stated on
 value = E_conv(total) / t_step, E_conv = edges of the four convolved relations (p->l, l->p, l->n, n->l),
 counted once per step.  t_step = max over ranks of (barrier + hipDeviceSynchronize
 bracketed K steps) / K (the bench contract); the median of the K per-step durations (HIP events between
-steps on the step's stream) is reported beside it.  N > 1 (components): after the timed region
-rank 0 alone also trains all the components the ranks split (2 warm-up + median of 5) and reports
+steps on the step's stream) is reported beside it.  N > 1 (components) with ``--full``: after the
+timed region rank 0 alone also trains all the components the ranks split (2 warm-up + median of 5) and reports
 ``scaling_vs_1gpu`` = that step time / this run's median step (ideal N).  The timed region runs no probes: the
-per-kernel HIP-event figures (``roofline``, ``gemm``) come from a separate untimed pass over the same step.
+per-kernel HIP-event figures (``roofline``, ``gemm``) come from a separate untimed pass over the same step (``--full``).
 
 Rank 0 prints one JSON line.
 """
@@ -64,6 +75,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: CSR-build times, the per-kernel probe pass, the "
+                         "extras (sampler / decoder / real loop / cfg5 / GAT), the N > 1 single-GPU reference and the "
+                         "CPU baseline (each still dropped by its --no-* switch)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write loss, parameters and gradients of the last timed step to "
+                         "DIR/<name>.npy (float32)")
     ap.add_argument("--config", default="cfg3",
                     help="cfg3 (default, BASELINE configs[2]; N > 1: cfg4's 8-component split), cfg4, cfg5 (bf16), "
                          "cfg2, cfg2bf (bf16 at cfg2 size)")
@@ -92,7 +110,10 @@ def parse():
                          "and cfg5 — the step is GPU-bound, the host runs ahead)")
     ap.add_argument("--launch-dry-run", action="store_true",
                     help="print the rank-launch decision for --gpus as JSON and exit (touches no GPU)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_plan(gpus: int, env, n_devices: int) -> dict:
@@ -735,6 +756,30 @@ def gemm_fields(m, bf16: bool, steps: int, t_step: float, what: str):
             "share_of_step": round(m["total_ms"] / steps / (t_step * 1e3), 4)}
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20   # --dump-outputs: upper bound on what one run writes
+
+
+def dump_outputs(directory: str, loss, model) -> dict:
+    """--dump-outputs: what the caller of the timed step holds after the last timed step, one float32 .npy each —
+    the returned loss, every parameter (after that step's optimizer update) and its gradient.  The model is a few MB
+    at every config, far below DUMP_LIMIT_BYTES; an array that would pass the limit is an error, not a silent cut."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(1)}
+    for name, p in model.named_parameters():
+        arrays[f"param.{name}"] = p.detach()
+        if p.grad is not None:
+            arrays[f"grad.{name}"] = p.grad.detach()
+    total = 0
+    for name, t in arrays.items():
+        a = t.to(device="cpu", dtype=torch.float32).contiguous().numpy()
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise SystemExit(f"--dump-outputs: {name} takes the dump past {DUMP_LIMIT_BYTES} bytes")
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+    return {"dir": directory, "files": len(arrays), "bytes": total}
+
+
 def main():
     args = parse()
     if not args.cpu_full:
@@ -827,7 +872,7 @@ def main():
             dist.barrier(device_ids=[dev.index]) if backend == "nccl" else dist.barrier()
 
     # the dst-range graph is a rank's share (local destination ids, global source ids): no standalone extras
-    no_extras = args.no_extras or partition == "dst-range"
+    no_extras = not args.full or args.no_extras or partition == "dst-range"
     csr_ms = None
     if rank == 0 and not no_extras:
         csr_ms = csr_build_ms(graph, dev)     # separate cold builds; the model builds its own cached copies
@@ -872,18 +917,22 @@ def main():
     final_loss = float(loss)
     if reducer is not None:
         reducer.check()   # one host sync after the timed region: every rank reduced the same parameter set
+    dumped = None
+    if rank == 0 and args.dump_outputs:   # parameters and reduced gradients are the same on every rank
+        dumped = dump_outputs(args.dump_outputs, loss, model)
 
     # untimed per-kernel pass: the same eager step with HIP events around the aggregate and GEMM launches
     probe = None
     steps_recorded = min(args.steps, 3)
-    if not args.no_probe:
+    if args.full and not args.no_probe:
         probe = profiling.start()
         for _ in range(steps_recorded):
             eager_step()
         profiling.stop()
 
     ref1 = None
-    if world > 1 and partition == "components" and args.skew == "uniform" and not (args.no_ref1 or args.prune_dead):
+    if (args.full and world > 1 and partition == "components" and args.skew == "uniform"
+            and not (args.no_ref1 or args.prune_dead)):
         if rank == 0:
             ref1 = one_gpu_reference(cfg, n_comp, dev, args.adam, args.graph)
         barrier()
@@ -939,7 +988,7 @@ def main():
         out = {"metric": METRIC, "value": round(value, 1), "unit": "edges/s", "n_gpus": world,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(t_step * 1e3, 4),
                "ms_per_step_median": round(t_med * 1e3, 4),
-               "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
+               "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "full": bool(args.full),
                "dtype": "bf16" if bf16 else "f32", "accumulate": "f32",
                "data": "synthetic: SURVEY.md §8.D generator (uniform endpoints, reverse relations = flips, randn "
                        "features, rand+0.5 labels), random-init weights (seed 1997)",
@@ -978,7 +1027,9 @@ def main():
         # the worst-case device footprint of this rank: its share, rank 0's all-component reference and the extras
         out["peak_device_mem_gb"] = round(torch.cuda.max_memory_allocated(dev) / 1e9, 2)
         out["peak_device_mem_gb_timed_per_rank"] = peak_per_rank
-        if world == 1 and not args.no_cpu_baseline:
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg)
         else:
             out["cpu_baseline"] = None

@@ -6,6 +6,6 @@ cd "$(dirname "$0")/.."
 OUT=gpurun_out/${TAG:-dist}
 mkdir -p "$OUT"
 HGIN_DIST_BACKEND=gloo timeout -k 10 ${DIST_TIMEOUT:-400} python -m torch.distributed.run --nnodes=1 \
-  --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 \
+  --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 --full \
   > "$OUT/bench_2rank_gloo.json" 2> "$OUT/bench_2rank_gloo.err"
 echo "dist_rehearsal $?" >> "$OUT/status.txt"

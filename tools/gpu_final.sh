@@ -20,7 +20,7 @@ if [ "${SUITE:-1}" = "1" ]; then
   step smoke 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')"
 fi
 [ "${EVID:-1}" = "1" ] || { echo done >> "$OUT/status.txt"; exit 0; }
-step bench 600 python bench.py --gpus 1 --steps 20 --warmup 5
+step bench 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full
 step prof_batches 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_batches" -o run -- \
     python3 tools/batches_prof.py --steps 200
 for C in cfg3 cfg5; do

@@ -12,8 +12,8 @@ step() {  # name, limit, command...
   local rc=$?; echo "$name $rc" >> "$OUT/status.txt"
   case $rc in 0) ;; *) echo "FATAL $name $rc"; tail -30 "$OUT/$name.log"; exit $rc ;; esac
 }
-step cfg5 400 python bench.py --config cfg5 --no-cpu-baseline
-step cfg4 400 python bench.py --config cfg4 --no-cpu-baseline --no-extras
-step zipf 500 python bench.py --skew zipf --no-cpu-baseline --no-extras
-step dst1 400 python bench.py --partition dst-range --no-cpu-baseline
+step cfg5 400 python bench.py --full --config cfg5 --no-cpu-baseline
+step cfg4 400 python bench.py --full --config cfg4 --no-cpu-baseline --no-extras
+step zipf 500 python bench.py --full --skew zipf --no-cpu-baseline --no-extras
+step dst1 400 python bench.py --full --partition dst-range --no-cpu-baseline
 echo done >> "$OUT/status.txt"

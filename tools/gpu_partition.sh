@@ -14,7 +14,7 @@ step() {  # name, limit, command...
   case $rc in 0) ;; *) echo "FATAL $name $rc"; tail -30 "$OUT/$name.log"; exit $rc ;; esac
 }
 step pytest_dist 400 python -u -m pytest tests/test_gpu_dist.py -x -v --timeout 300 --timeout-method thread
-step bench_dst1 400 python bench.py --partition dst-range --no-cpu-baseline
+step bench_dst1 400 python bench.py --full --partition dst-range --no-cpu-baseline
 HGIN_DIST_BACKEND=gloo step bench_dst2_gloo 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
   --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 --config cfg2 \
   --partition dst-range --no-probe

@@ -13,7 +13,7 @@ run() {
   [ $rc -eq 0 ] || { echo "FATAL $name $rc"; tail -20 "$OUT/$name.err"; exit $rc; }
 }
 for C in ${CONFIGS:-cfg3}; do
-  if [ "${BENCH:-0}" = "1" ]; then run bench_$C 600 python bench.py --config $C ${BENCH_ARGS:-}; fi
+  if [ "${BENCH:-0}" = "1" ]; then run bench_$C 600 python bench.py --full --config $C ${BENCH_ARGS:-}; fi
   run prof_$C 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$C" -o run -- \
       python3 bench.py --config $C --no-cpu-baseline --no-probe --no-extras ${BENCH_ARGS:-}
   f=$(ls "$OUT"/prof_$C/*/run_kernel_stats.csv 2>/dev/null | head -1)

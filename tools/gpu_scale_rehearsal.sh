@@ -9,7 +9,7 @@ OUT=gpurun_out/${TAG:-scale_rehearsal}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 HGIN_DIST_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 --no-probe \
+  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 --full --no-probe \
   > "$OUT/bench_2rank.json" 2> "$OUT/bench_2rank.err"
 rc=$?; echo "bench_2rank $rc" >> "$OUT/status.txt"
 tail -1 "$OUT/bench_2rank.json"; exit $rc

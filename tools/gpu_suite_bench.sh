@@ -17,7 +17,7 @@ if [ "${SUITE:-1}" = "1" ]; then
   run pytest_gpu ${PYTEST_LIMIT:-900} python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread -rP
 fi
 for C in ${CONFIGS:-cfg3}; do
-  run bench_$C 600 python bench.py --config $C ${BENCH_ARGS:-}
+  run bench_$C 600 python bench.py --full --config $C ${BENCH_ARGS:-}
 done
 echo "done $(date)" >> "$OUT/status.txt"
 tail -3 "$OUT/pytest_gpu.out" 2>/dev/null
