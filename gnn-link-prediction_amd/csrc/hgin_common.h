@@ -104,16 +104,25 @@ using bf16x2_t = __attribute__((ext_vector_type(2))) __bf16;
 __device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2_t{lo, hi}, bf16x2_t));
 }
+// keep_scalar: an empty asm that takes the two values as separate scalar operands, so the SLP vectoriser (plain -O3)
+// does not fuse the two operations that made them into one packed fp32 instruction (v_pk_add_f32 / v_pk_mul_f32).
+// Packed fp32 VALU issued beside MFMAs stalls the matrix pipe (MI355X: +22..26 cycles per MFMA gap), so the
+// weight-stationary loops pin their split and PReLU arithmetic; scalar and packed fp32 round alike.
+__device__ __forceinline__ void keep_scalar(float& a, float& b) { asm("" : "+v"(a), "+v"(b)); }
+template <bool kPin = false>
 __device__ __forceinline__ void split2(float x0, float x1, uint32_t& p1, uint32_t& p2, uint32_t& p3) {
   p1 = cvt_pk_bf16(x0, x1);
-  const float r0 = x0 - bf_lo(p1), r1 = x1 - bf_hi(p1);
+  float r0 = x0 - bf_lo(p1), r1 = x1 - bf_hi(p1);
+  if constexpr (kPin) keep_scalar(r0, r1);
   p2 = cvt_pk_bf16(r0, r1);
-  const float s0 = r0 - bf_lo(p2), s1 = r1 - bf_hi(p2);
+  float s0 = r0 - bf_lo(p2), s1 = r1 - bf_hi(p2);
+  if constexpr (kPin) keep_scalar(s0, s1);
   p3 = cvt_pk_bf16(s0, s1);
 }
+template <bool kPin = false>
 __device__ __forceinline__ void split4(const float4 v, uint2 (&o)[3]) {
-  split2(v.x, v.y, o[0].x, o[1].x, o[2].x);
-  split2(v.z, v.w, o[0].y, o[1].y, o[2].y);
+  split2<kPin>(v.x, v.y, o[0].x, o[1].x, o[2].x);
+  split2<kPin>(v.z, v.w, o[0].y, o[1].y, o[2].y);
 }
 // LDS row of a split operand: 3 planes x 32 bf16 (one 32-deep K-tile) + 16 B pad = 208 B = 13 x 16 B, so the
 // 16 rows of a ds_read_b128 lane group fall on 16 distinct 16-B bank slots (13 is odd).
@@ -133,6 +142,17 @@ __device__ __forceinline__ void glds16_asm(const void* g, void* lds_wave_base) {
     asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off nt" ::"v"(g), "s"(m0) : "memory", "m0");
   else
     asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(m0) : "memory", "m0");
+}
+
+// The same DMA in its saddr form, for steady-state loops: a wave-uniform 64-bit base (SGPR pair) plus a 32-bit
+// unsigned per-lane byte offset, and the LDS address handed over as an already uniform value — nothing per DMA but
+// the s_mov of m0 (no 64-bit lane address, no v_readfirstlane).  Non-temporal.
+__device__ __forceinline__ void glds16_asm_s(const void* wave_base, uint32_t lane_off, uint32_t lds_wave_addr) {
+  asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1 nt"
+               ::"v"(lane_off), "s"(wave_base), "s"(lds_wave_addr) : "memory", "m0");
+}
+__device__ __forceinline__ uint32_t lds_addr32(const void* p) {
+  return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)(p);
 }
 
 template <int N>

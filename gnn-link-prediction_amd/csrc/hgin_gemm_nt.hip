@@ -1830,7 +1830,7 @@ __global__ __launch_bounds__(512, 1) void k_wss_f32(WsArgs32 g) {
       const int grp = ((wave * C::PA + q) * 1024 + ln * 16) / 16;
       const int r = grp / (K / 4), k = (grp % (K / 4)) * 4;
       uint2 o[3];
-      split4(v[q], o);
+      split4<EPI == 4>(v[q], o);   // (the dX form: its residual subtractions were SLP-packed; the others never were)
       const int off = r * C::PROW + 16 * ((k >> 3) ^ (r & C::SW)) + 8 * ((k >> 2) & 1);
 #pragma unroll
       for (int p = 0; p < 3; ++p) *reinterpret_cast<uint2*>(pl + p * C::PL + off) = o[p];

@@ -8,6 +8,8 @@
 // the result is bitwise reproducible.
 #include "hgin_common.h"
 
+#include <type_traits>
+
 namespace hgin {
 namespace {
 
@@ -782,7 +784,7 @@ __global__ __launch_bounds__(512, 1) void k_wsd_bf16(const uint16_t* __restrict_
                                                      const uint16_t* __restrict__ B1, int64_t ldb1,
                                                      const uint16_t* __restrict__ B2, int64_t ldb2, int64_t K1,
                                                      int64_t M, float* __restrict__ slab, int64_t ld_slab,
-                                                     bool nt_in, WsdPro pro) {
+                                                     WsdPro pro) {
   using C = WsdCfg<N, K, PRO>;
   constexpr int NST = C::NST;
   extern __shared__ __attribute__((aligned(16))) char wsd_smem[];
@@ -800,9 +802,7 @@ __global__ __launch_bounds__(512, 1) void k_wsd_bf16(const uint16_t* __restrict_
     asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(tid));
     return t;
   };
-  auto dma = [&](const void* src, void* dst) {
-    if (nt_in) glds16_asm<true>(src, dst); else glds16_asm(src, dst);
-  };
+  auto dma = [&](const void* src, void* dst) { glds16_asm<true>(src, dst); };   // non-temporal: the rows stream
   const int k1 = (int)K1;
   const float sl = PRO ? pro.slope[0] : 0.0f;
   const bool zy = PRO && pro.yalt != nullptr && sl > 0.0f;   // (wave-uniform)
@@ -1040,8 +1040,7 @@ template <int N, int K, bool PRO>
 __global__ __launch_bounds__(512, 1) void k_wsd_f32(const float* __restrict__ A, int64_t lda,
                                                     const float* __restrict__ B1, int64_t ldb1,
                                                     const float* __restrict__ B2, int64_t ldb2, int64_t K1, int64_t M,
-                                                    float* __restrict__ slab, int64_t ld_slab, bool nt_in,
-                                                    WsdPro pro) {
+                                                    float* __restrict__ slab, int64_t ld_slab, WsdPro pro) {
   using C = WsdF32Cfg<N, K, PRO>;
   constexpr int NST = C::NST;
   extern __shared__ __attribute__((aligned(16))) char wsdf_smem[];
@@ -1060,10 +1059,9 @@ __global__ __launch_bounds__(512, 1) void k_wsd_f32(const float* __restrict__ A,
     asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(tid));
     return t;
   };
-  auto dma = [&](const void* src, void* dst) {
-    if (nt_in) glds16_asm<true>(src, dst); else glds16_asm(src, dst);
-  };
+  auto dma = [&](const void* src, void* dst) { glds16_asm<true>(src, dst); };   // non-temporal: the rows stream
   const int k1 = (int)K1;
+  // The clamped form: any block, rows past M included (start-up and a workgroup's last block only; see k_wsp_f32).
   auto issue = [&](int64_t i) {
     char* base = wsdf_smem + (int)(i % NST) * C::SLOT;
     const int64_t r0 = ((int64_t)blockIdx.x + i * G) * C::BM;
@@ -1094,6 +1092,61 @@ __global__ __launch_bounds__(512, 1) void k_wsd_f32(const float* __restrict__ A,
           base + C::A_BYTES + C::Z_BYTES + piece * 1024);
     }
   };
+  // The steady state's form of the same DMAs (whole blocks): g_y, z and the g_z store go through a wave-uniform
+  // block pointer (SGPRs) that advances by G blocks per block plus a constant 32-bit lane offset (row * ld + column,
+  // ld < 2^24); a lane's piece of B may come from b1 or b2, so each B piece keeps a per-lane pointer and the lane's
+  // stride.  NCL: the pieces that differ in their columns (the others differ only in the row).
+  constexpr int NCL = K * 4 > 1024 ? K * 4 / 1024 : 1;
+  static_assert(C::PB % NCL == 0, "a wave's B pieces start on a row");
+  const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+  const uint32_t lds0 = lds_addr32(wsdf_smem);
+  const int64_t rb_i = ((int64_t)blockIdx.x + (NST - 1) * G) * C::BM;   // the first steady-state issue: block NST - 1
+  const char* s_a = reinterpret_cast<const char*>(A + rb_i * lda);
+  const char* s_z = PRO ? reinterpret_cast<const char*>(static_cast<const float*>(pro.z) + rb_i * pro.ldz) : nullptr;
+  char* s_gz = PRO ? reinterpret_cast<char*>(static_cast<float*>(pro.gz) + (int64_t)blockIdx.x * C::BM * pro.ldgz)
+                   : nullptr;
+  const int64_t st_a = G * C::BM * lda * 4, st_z = PRO ? G * C::BM * pro.ldz * 4 : 0,
+                st_gz = PRO ? G * C::BM * pro.ldgz * 4 : 0;
+  uint32_t o_a[C::PA], o_z[C::PA];
+#pragma unroll
+  for (int q = 0; q < C::PA; ++q) {
+    const int off = (wave * C::PA + q) * 1024 + lane * 16;
+    const int r = off / (N * 4), c = (off % (N * 4)) / 4;
+    o_a[q] = 4u * (uint32_t)(r * (int)lda + c);
+    o_z[q] = PRO ? 4u * (uint32_t)(r * (int)pro.ldz + c) : 0u;
+  }
+  const char* v_b[NCL];     // this lane's 16 B of the wave's first row of B, per column piece
+  uint32_t ld_b[NCL];       // and the leading dimension of the source they come from (32 x 32 -> 64-bit strides)
+#pragma unroll
+  for (int q = 0; q < NCL; ++q) {
+    const int off = (wave * C::PB + q) * 1024 + lane * 16;
+    const int r = off / (K * 4), k = (off % (K * 4)) / 4;
+    const bool from1 = k < k1;
+    ld_b[q] = (uint32_t)(from1 ? ldb1 : ldb2);
+    v_b[q] = reinterpret_cast<const char*>((from1 ? B1 + k : B2 + (k - k1)) + (rb_i + r) * (int64_t)ld_b[q]);
+  }
+  const uint32_t st_b = (uint32_t)(G * C::BM * 4);   // bytes per unit of ld per block step (G <= the CU count)
+  int fslot = NST - 1;   // ring slot of the next steady-state issue
+  auto issue_whole = [&]() {
+    const uint32_t base = lds0 + (uint32_t)fslot * C::SLOT;
+#pragma unroll
+    for (int q = 0; q < C::PA; ++q) {
+      glds16_asm_s(s_a, o_a[q], base + (uint32_t)(wave_s * C::PA + q) * 1024u);
+      if constexpr (PRO) glds16_asm_s(s_z, o_z[q], base + C::A_BYTES + (uint32_t)(wave_s * C::PA + q) * 1024u);
+    }
+#pragma unroll
+    for (int q = 0; q < C::PB; ++q) {
+      asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off nt"
+                   ::"v"(v_b[q % NCL] + (uint64_t)ld_b[q % NCL] * (uint32_t)(4 * (q / NCL))),
+                     "s"(base + C::A_BYTES + C::Z_BYTES + (uint32_t)(wave_s * C::PB + q) * 1024u)
+                   : "memory", "m0");
+    }
+#pragma unroll
+    for (int q = 0; q < NCL; ++q) v_b[q] += (uint64_t)ld_b[q] * st_b;
+    s_a += st_a;
+    if constexpr (PRO) s_z += st_z;
+    fslot = fslot + 1 == NST ? 0 : fslot + 1;
+  };
   float csum[4];
   float ssum = 0.0f;
   const float sl = PRO ? pro.slope[0] : 0.0f;
@@ -1118,56 +1171,83 @@ __global__ __launch_bounds__(512, 1) void k_wsd_f32(const float* __restrict__ A,
   for (int i = 0; i < NST - 1; ++i)
     if (i < my) issue(i);
 
-  for (int64_t i = 0; i < my; ++i) {
-    if (i + NST - 2 < my) {
+  uint32_t o_gz[C::S > 0 ? C::S : 1];   // steady-state g_z store: lane offsets from the block pointer
+#pragma unroll
+  for (int q = 0; q < C::S; ++q) {
+    const int e0 = (q * C::NT + tid) * 4;
+    o_gz[q] = 4u * (uint32_t)((e0 / N) * (int)pro.ldgz + e0 % N);
+  }
+  int uslot = 0;   // ring slot of the block being consumed
+  // One block: wait for it, refill the slot freed by the previous one, split, multiply.  kTail: block i may hold rows
+  // past M (a workgroup's last block).  kNext: 0 = nothing left to issue, 1 = the refill is a whole block (the steady
+  // state: no per-row predicate, no address rebuilt), 2 = the refill, if there is one, may be the last block.
+  // kWarm: i >= NST - 1 and i + NST - 2 < my, so the vmcnt bound is the ring's constant one.
+  auto block = [&](auto tail, auto next, auto warm, int64_t i) {
+    constexpr bool kTail = decltype(tail)::value;
+    constexpr int kNext = decltype(next)::value;
+    if constexpr (decltype(warm)::value) {
+      wait_vm<(NST - 2) * C::P + (NST - 1) * C::S>();
+    } else if (i + NST - 2 < my) {
       wsd_wait<NST, C::P, C::S>(i);
     } else {
       wait_vm<0>();
     }
     __builtin_amdgcn_s_barrier();   // block i landed for every wave; slot i-1 and the plane images are free
     asm volatile("" ::: "memory");
-    if (i + NST - 1 < my) issue(i + NST - 1);
-    const char* fbase = wsdf_smem + (int)(i % NST) * C::SLOT;
-    const int64_t r0 = ((int64_t)blockIdx.x + i * G) * C::BM;
-    const int valid = M - r0 < C::BM ? (int)(M - r0) : C::BM;
+    if constexpr (kNext == 1) issue_whole();
+    if constexpr (kNext == 2)
+      if (i + NST - 1 < my) issue(i + NST - 1);
+    const char* fbase = wsdf_smem + uslot * C::SLOT;
+    uslot = uslot + 1 == NST ? 0 : uslot + 1;
+    const int64_t r0 = kTail ? ((int64_t)blockIdx.x + i * G) * C::BM : 0;
+    const int valid = kTail ? (M - r0 < C::BM ? (int)(M - r0) : C::BM) : C::BM;
     {   // split both fp32 images into three bf16 planes, one float4 (half a 16-B plane chunk) per lane and step:
         // consecutive lanes read consecutive 16-B pieces (conflict-free; 32 B per lane was 2-way conflicted)
       const int t = tid_o();
       constexpr int CA = C::CA, CT = C::BM * (N + K) / 4;   // float4 groups
+      static_assert(CT % C::NT == 0 && CA % C::NT == 0, "every thread the same groups, A first");
 #pragma unroll
-      for (int q = 0; q < (CT + C::NT - 1) / C::NT; ++q) {
+      for (int q = 0; q < CT / C::NT; ++q) {
         const int grp = q * C::NT + t;
-        if (CT % C::NT != 0 && grp >= CT) break;
-        const bool isA = grp < CA;
+        const bool isA = q < CA / C::NT;
         const int e0 = (isA ? grp : grp - CA) * 4;
         const int row = isA ? e0 / N : e0 / K, col = isA ? e0 % N : e0 % K;   // constant divisors: shifts
         const float* src = reinterpret_cast<const float*>(fbase + (isA ? 0 : C::A_BYTES + C::Z_BYTES)) + e0;
         float4 v = *reinterpret_cast<const float4*>(src);
-        if (row >= valid) v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (kTail && row >= valid) v = make_float4(0.f, 0.f, 0.f, 0.f);
         if constexpr (PRO) {
           if (isA) {   // g_z from g_y and z; its store; the partial sums (columns fixed per thread)
             const float* zs = reinterpret_cast<const float*>(fbase + C::A_BYTES) + e0;
             float4 z4 = *reinterpret_cast<const float4*>(zs);
-            if (row >= valid) z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (kTail && row >= valid) z4 = make_float4(0.f, 0.f, 0.f, 0.f);
             float gg[4] = {v.x, v.y, v.z, v.w};
             const float zz[4] = {z4.x, z4.y, z4.z, z4.w};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
               const bool pos = zz[j] > 0.0f;
-              const float o = pos ? gg[j] : __fmul_rn(sl, gg[j]);
+              float sg = __fmul_rn(sl, gg[j]);   // (chained through keep_scalar: no two of these multiplies can pair up)
+              keep_scalar(sg, gg[j]);
+              float zg = __fmul_rn(zz[j], gg[j]);
+              keep_scalar(zg, gg[(j + 1) & 3]);
+              const float o = pos ? gg[j] : sg;
               csum[j] = __fadd_rn(csum[j], o);
-              if (!pos) ssum = __fadd_rn(ssum, __fmul_rn(zz[j], gg[j]));
+              keep_scalar(csum[j], csum[(j + 1) & 3]);
+              if (!pos) ssum = __fadd_rn(ssum, zg);
               gg[j] = o;
             }
             v = make_float4(gg[0], gg[1], gg[2], gg[3]);
-            const int64_t gr = r0 + row;
-            float* gzp = gr < M ? static_cast<float*>(pro.gz) + gr * pro.ldgz + col
-                                : reinterpret_cast<float*>(pro.dump + (int64_t)t * 32 + 16 * q);
-            *reinterpret_cast<float4*>(gzp) = v;
+            if constexpr (kTail) {
+              const int64_t gr = r0 + row;
+              float* gzp = gr < M ? static_cast<float*>(pro.gz) + gr * pro.ldgz + col
+                                  : reinterpret_cast<float*>(pro.dump + (int64_t)t * 32 + 16 * q);
+              *reinterpret_cast<float4*>(gzp) = v;
+            } else {
+              *reinterpret_cast<float4*>(s_gz + o_gz[q < C::S ? q : 0]) = v;
+            }
           }
         }
         uint2 o[3];
-        split4(v, o);
+        split4<true>(v, o);
         const int prow = isA ? C::PA_ROW : C::PB_ROW;
         char* pl = planes + (isA ? 0 : 3 * C::PA_BYTES);
         const int pbytes = isA ? C::PA_BYTES : C::PB_BYTES;
@@ -1216,7 +1296,28 @@ __global__ __launch_bounds__(512, 1) void k_wsd_f32(const float* __restrict__ A,
     }
     __builtin_amdgcn_s_setprio(0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  }
+    if constexpr (PRO && !kTail) s_gz += st_gz;
+  };
+  using Tail = std::true_type;
+  using Whole = std::false_type;
+  using Warm = std::true_type;
+  using Cold = std::false_type;
+  int64_t i = 0;
+#pragma unroll
+  for (int t = 0; t < NST - 1; ++t)   // (not a loop: the ring fills, fewer stores in flight than the steady bound counts)
+    if (i + NST < my) {
+      block(Whole{}, std::integral_constant<int, 1>{}, Cold{}, i);
+      ++i;
+    }
+  for (; i + NST < my; ++i)           // the steady state; refill i + NST - 1 <= my - 2: a whole block
+    block(Whole{}, std::integral_constant<int, 1>{}, Warm{}, i);
+#pragma unroll
+  for (int t = 0; t < NST - 1; ++t)   // (not a loop: the last NST - 1 whole blocks, whose refill may be the last block)
+    if (i + 1 < my) {
+      block(Whole{}, std::integral_constant<int, 2>{}, Cold{}, i);
+      ++i;
+    }
+  block(Tail{}, std::integral_constant<int, 0>{}, Cold{}, my - 1);
   if constexpr (PRO) {   // fixed-order workgroup sums: column n over the threads that own it, the slope over all
     wait_vm<0>();
     __builtin_amdgcn_s_barrier();
@@ -1283,8 +1384,7 @@ template <bool PRO>
 __global__ __launch_bounds__(512, 1) void k_wsp_f32(const float* __restrict__ A, int64_t lda,
                                                     const float* __restrict__ B1, int64_t ldb1,
                                                     const float* __restrict__ B2, int64_t ldb2, int64_t K1, int64_t M,
-                                                    float* __restrict__ slab, int64_t ld_slab, bool nt_in,
-                                                    WsdPro pro) {
+                                                    float* __restrict__ slab, int64_t ld_slab, WsdPro pro) {
   using C = WspF32Cfg;
   constexpr int N = C::N, K = C::K;
   constexpr int Z_OFF = C::A_BYTES, B_OFF = C::A_BYTES * (PRO ? 2 : 1);
@@ -1292,6 +1392,7 @@ __global__ __launch_bounds__(512, 1) void k_wsp_f32(const float* __restrict__ A,
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
+  const int wave_s = __builtin_amdgcn_readfirstlane(wave);   // (scalar: the per-wave addresses below live in SGPRs)
   const int wm = wave % C::WM, wk = wave / C::WM;
   const int64_t nblk = (M + C::BM - 1) / C::BM;
   const int64_t G = gridDim.x;
@@ -1304,36 +1405,68 @@ __global__ __launch_bounds__(512, 1) void k_wsp_f32(const float* __restrict__ A,
     asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(tid));
     return t;
   };
-  auto dma = [&](const void* src, void* dst) {
-    if (nt_in) glds16_asm<true>(src, dst); else glds16_asm(src, dst);
-  };
   const int k1 = (int)K1;
-  auto issue = [&](int64_t i) {   // this wave's slice of block i: g_y [, z] and B pieces
-    const int64_t r0 = ((int64_t)blockIdx.x + i * G) * C::BM;
-    const int rmax = (int)(M - 1 - r0 < C::BM ? M - 1 - r0 : C::BM - 1);
-    const int ln = tid_o() & 63;
-    const float* ab = A + r0 * lda;
-    const float* b1 = B1 + r0 * ldb1;
-    const float* b2 = B2 + r0 * ldb2;
+  // Only a workgroup's last block can hold rows past M, so the row clamps, the zeroing of invalid rows and the dump
+  // slot exist only in the kTail instantiations of issue / split (block 0's start-up and the last block); the
+  // steady state runs the other ones, which have no per-row predicate and rebuild no address.
+  // Steady-state sources: wave w DMAs rows 2 w, 2 w + 1 of every image, lane l 16 B at column 4 l.  g_y, z and the
+  // g_z store go through a wave-uniform row pointer (SGPRs) that advances by G blocks per block, plus the constant
+  // lane offset 16 l; a lane's half of B may come from b1 or b2, so B keeps a per-lane pointer and stride.
+  const int64_t rw0 = (int64_t)blockIdx.x * C::BM + 2 * wave_s;        // this wave's first row of block 0
+  const uint32_t lane16 = 16u * (uint32_t)lane;
+  const uint32_t lds_w = lds_addr32(wsp_smem) + (uint32_t)wave_s * 2048u;   // this wave's slice of each image
+  const char* s_a = reinterpret_cast<const char*>(A + (rw0 + 2 * G * C::BM) * lda);   // (first fast issue: block 2)
+  const char* s_z = PRO ? reinterpret_cast<const char*>(static_cast<const float*>(pro.z) + (rw0 + 2 * G * C::BM) * pro.ldz)
+                        : nullptr;
+  char* s_gz = PRO ? reinterpret_cast<char*>(static_cast<float*>(pro.gz) + (rw0 + G * C::BM) * pro.ldgz) : nullptr;
+  const bool from1 = 4 * lane < k1;
+  const int64_t ldb_l = from1 ? ldb1 : ldb2;
+  const char* v_b = reinterpret_cast<const char*>((from1 ? B1 + 4 * lane : B2 + (4 * lane - k1)) +
+                                                  (rw0 + 2 * G * C::BM) * ldb_l);
+  const int64_t st_a = G * C::BM * lda * 4, st_z = PRO ? G * C::BM * pro.ldz * 4 : 0,
+                st_gz = PRO ? G * C::BM * pro.ldgz * 4 : 0, st_b = G * C::BM * ldb_l * 4;
+  auto issue = [&](auto tail, int64_t i) {   // this wave's slice of block i: g_y [, z] and B pieces
+    if constexpr (decltype(tail)::value) {
+      const int64_t r0 = ((int64_t)blockIdx.x + i * G) * C::BM;
+      const int rmax = (int)(M - 1 - r0 < C::BM ? M - 1 - r0 : C::BM - 1);
+      const int ln = tid_o() & 63;
+      const float* ab = A + r0 * lda;
+      const float* b1 = B1 + r0 * ldb1;
+      const float* b2 = B2 + r0 * ldb2;
 #pragma unroll
-    for (int q = 0; q < C::PA; ++q) {
-      const int piece = wave * C::PA + q;
-      const int off = piece * 1024 + ln * 16;
-      int r = off / (N * 4);
-      r = r < rmax ? r : rmax;                       // (rows past M are zeroed at the split)
-      dma(ab + (r * (int)lda + (off % (N * 4)) / 4), wsp_smem + piece * 1024);
-      if constexpr (PRO)
-        dma(static_cast<const float*>(pro.z) + (r0 + r) * pro.ldz + (off % (N * 4)) / 4,
-            wsp_smem + Z_OFF + piece * 1024);
-    }
+      for (int q = 0; q < C::PA; ++q) {
+        const int piece = wave * C::PA + q;
+        const int off = piece * 1024 + ln * 16;
+        int r = off / (N * 4);
+        r = r < rmax ? r : rmax;                       // (rows past M are zeroed at the split)
+        glds16_asm<true>(ab + (r * (int)lda + (off % (N * 4)) / 4), wsp_smem + piece * 1024);
+        if constexpr (PRO)
+          glds16_asm<true>(static_cast<const float*>(pro.z) + (r0 + r) * pro.ldz + (off % (N * 4)) / 4,
+                           wsp_smem + Z_OFF + piece * 1024);
+      }
 #pragma unroll
-    for (int q = 0; q < C::PB; ++q) {
-      const int piece = wave * C::PB + q;
-      const int off = piece * 1024 + ln * 16;
-      int r = off / (K * 4);
-      r = r < rmax ? r : rmax;
-      const int k = (off % (K * 4)) / 4;
-      dma(k < k1 ? b1 + (r * (int)ldb1 + k) : b2 + (r * (int)ldb2 + (k - k1)), wsp_smem + B_OFF + piece * 1024);
+      for (int q = 0; q < C::PB; ++q) {
+        const int piece = wave * C::PB + q;
+        const int off = piece * 1024 + ln * 16;
+        int r = off / (K * 4);
+        r = r < rmax ? r : rmax;
+        const int k = (off % (K * 4)) / 4;
+        glds16_asm<true>(k < k1 ? b1 + (r * (int)ldb1 + k) : b2 + (r * (int)ldb2 + (k - k1)),
+                         wsp_smem + B_OFF + piece * 1024);
+      }
+    } else {   // (the same DMAs in the same order; i is the block the running pointers stand at)
+#pragma unroll
+      for (int q = 0; q < C::PA; ++q) {
+        glds16_asm_s(s_a + q * (lda * 4), lane16, lds_w + q * 1024);
+        if constexpr (PRO) glds16_asm_s(s_z + q * (pro.ldz * 4), lane16, lds_w + Z_OFF + q * 1024);
+      }
+#pragma unroll
+      for (int q = 0; q < C::PB; ++q)
+        asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off nt"
+                     ::"v"(v_b + q * (ldb_l * 4)), "s"(lds_w + B_OFF + q * 1024) : "memory", "m0");
+      s_a += st_a;
+      if constexpr (PRO) s_z += st_z;
+      v_b += st_b;
     }
   };
   float csum[4];
@@ -1361,11 +1494,15 @@ __global__ __launch_bounds__(512, 1) void k_wsp_f32(const float* __restrict__ A,
   // ds_read_b128 of the slice is 64 consecutive 16-B pieces (conflict-free; the earlier 32-B-per-lane reads were 2-way
   // conflicted: SQ_LDS_BANK_CONFLICT 32 % of the LDS-active cycles, profiles/r04/gpu_b/gemm_pmc2_sq.txt), and each
   // plane row half-chunk goes out as one ds_write_b64 (16 contiguous lanes = 128 contiguous bytes).
-  auto split = [&](int64_t j) {
+  // kTail: block j may hold rows past M.  kNext: 0 = block j is the last, 1 = the refill is a steady-state issue,
+  // 2 = the refill is the clamped issue (block j + 1 is the last, or the start-up, where j + 1 may not exist).
+  auto split = [&](auto tail, auto next, int64_t j) {
+    constexpr bool kTail = decltype(tail)::value;
+    constexpr int kNext = decltype(next)::value;
     wait_vm<0>();                                    // this wave's pieces of block j (and its older stores)
     char* pl = planes0 + (int)(j & 1) * C::PLANES;
-    const int64_t r0 = ((int64_t)blockIdx.x + j * G) * C::BM;
-    const int valid = M - r0 < C::BM ? (int)(M - r0) : C::BM;
+    const int64_t r0 = kTail ? ((int64_t)blockIdx.x + j * G) * C::BM : 0;
+    const int valid = kTail ? (M - r0 < C::BM ? (int)(M - r0) : C::BM) : C::BM;
     const int ln = tid_o() & 63;
     const int rw = 2 * wave;
     float4 va[2], vb[2], zv[2];
@@ -1377,37 +1514,50 @@ __global__ __launch_bounds__(512, 1) void k_wsp_f32(const float* __restrict__ A,
       zv[h] = PRO ? *reinterpret_cast<const float4*>(wsp_smem + Z_OFF + o) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the slice is read: refill it
-    if (j + 1 < my) issue(j + 1);
+    if constexpr (kNext == 1) issue(std::false_type{}, j + 1);
+    if constexpr (kNext == 2)
+      if (j + 1 < my) issue(std::true_type{}, j + 1);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int row = rw + h;
-      if (row >= valid) va[h] = vb[h] = zv[h] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (kTail)
+        if (row >= valid) va[h] = vb[h] = zv[h] = make_float4(0.f, 0.f, 0.f, 0.f);
       if constexpr (PRO) {   // g_z from g_y and z; its store; the partial sums (k_rows_bwd<0>'s arithmetic)
         float gg[4] = {va[h].x, va[h].y, va[h].z, va[h].w};
         const float zz[4] = {zv[h].x, zv[h].y, zv[h].z, zv[h].w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const bool pos = zz[e] > 0.0f;
-          const float o = pos ? gg[e] : __fmul_rn(sl, gg[e]);
+          float sg = __fmul_rn(sl, gg[e]);   // (chained through keep_scalar: no two of these multiplies can pair up)
+          keep_scalar(sg, gg[e]);
+          float zg = __fmul_rn(zz[e], gg[e]);
+          keep_scalar(zg, gg[(e + 1) & 3]);
+          const float o = pos ? gg[e] : sg;
           csum[e] = __fadd_rn(csum[e], o);
-          if (!pos) ssum = __fadd_rn(ssum, __fmul_rn(zz[e], gg[e]));
+          if (!pos) ssum = __fadd_rn(ssum, zg);
           gg[e] = o;
         }
         va[h] = make_float4(gg[0], gg[1], gg[2], gg[3]);
-        const int64_t gr = r0 + row;
-        float* gzp = gr < M ? static_cast<float*>(pro.gz) + gr * pro.ldgz + 4 * ln
-                            : reinterpret_cast<float*>(pro.dump + (int64_t)(wave * 64 + ln) * 32 + 16 * h);
-        *reinterpret_cast<float4*>(gzp) = va[h];
+        if constexpr (kTail) {
+          const int64_t gr = r0 + row;
+          float* gzp = gr < M ? static_cast<float*>(pro.gz) + gr * pro.ldgz + 4 * ln
+                              : reinterpret_cast<float*>(pro.dump + (int64_t)(wave * 64 + ln) * 32 + 16 * h);
+          *reinterpret_cast<float4*>(gzp) = va[h];
+        } else {
+          *reinterpret_cast<float4*>(s_gz + h * (pro.ldgz * 4) + lane16) = va[h];
+        }
       }
       const int off = C::PA_ROW * row + 16 * ((ln >> 1) ^ wsd_swz(row)) + 8 * (ln & 1);   // PA_ROW == PB_ROW
       uint2 o[3];
-      split4(va[h], o);
+      split4<true>(va[h], o);
 #pragma unroll
       for (int p = 0; p < 3; ++p) *reinterpret_cast<uint2*>(pl + p * C::PA_BYTES + off) = o[p];
-      split4(vb[h], o);
+      split4<true>(vb[h], o);
 #pragma unroll
       for (int p = 0; p < 3; ++p) *reinterpret_cast<uint2*>(pl + 3 * C::PA_BYTES + p * C::PB_BYTES + off) = o[p];
     }
+    if constexpr (PRO && !kTail) s_gz += st_gz;
   };
   // block i's products from plane buffer i & 1 (k_wsd_f32's fragments and order)
   auto mfma = [&](int64_t i) {
@@ -1447,21 +1597,30 @@ __global__ __launch_bounds__(512, 1) void k_wsp_f32(const float* __restrict__ A,
     }
   };
 
-  issue(0);
-  split(0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  for (int64_t i = 0; i + 1 < my; ++i) {
+  using Tail = std::true_type;
+  using Full = std::false_type;
+  auto step = [&](auto tail, auto next, int64_t i) {   // products of block i beside the split of block i + 1
     __builtin_amdgcn_s_barrier();   // planes of block i written by every wave; those of block i - 1 read by every wave
     asm volatile("" ::: "memory");
     if (wave < 4) {
-      split(i + 1);
+      split(tail, next, i + 1);
       mfma(i);
     } else {
       mfma(i);
-      split(i + 1);
+      split(tail, next, i + 1);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's plane writes and fragment reads are done
+  };
+  issue(Tail{}, 0);
+  split(Tail{}, std::integral_constant<int, 2>{}, 0);   // (refills with block 1 through the clamped issue)
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  int64_t i = 0;
+  for (; i + 3 < my; ++i) step(Full{}, std::integral_constant<int, 1>{}, i);   // blocks i + 1, i + 2 <= my - 2: whole
+  if (i + 2 < my) {   // block my - 2 is whole; its refill is the last block
+    step(Full{}, std::integral_constant<int, 2>{}, i);
+    ++i;
   }
+  if (i + 1 < my) step(Tail{}, std::integral_constant<int, 0>{}, i);   // the last block
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   mfma(my - 1);
@@ -1535,14 +1694,14 @@ template <int NV, int KV, bool PRO = false>
 int64_t launch_wsd(const uint16_t* a, int64_t lda, const uint16_t* b1, int64_t ldb1, const uint16_t* b2,
                    int64_t ldb2, int64_t k1, int64_t M, float* slab, int64_t ld_slab, int64_t grid, hipStream_t s,
                    const WsdPro& pro = WsdPro{}) {
-  constexpr bool nt = true;   // non-temporal DMA of the streamed rows (1-3 % faster, profiles/r02/gemm_ws_bf16.txt)
+  // (the streamed rows are DMA'd non-temporal: 1-3 % faster, profiles/r02/gemm_ws_bf16.txt)
   constexpr int lds = WsdCfg<NV, KV, PRO>::SLOT * WsdCfg<NV, KV, PRO>::NST;
   auto kern = k_wsd_bf16<NV, KV, PRO>;
   static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (attr != hipSuccess) return 0;
   HGIN_TRACE("k_wsd_bf16<%d,%d%s>", NV, KV, PRO ? ",prelu_bwd_fused" : "");
-  kern<<<(unsigned)grid, 512, lds, s>>>(a, lda, b1, ldb1, b2, ldb2, k1, M, slab, ld_slab, nt, pro);
+  kern<<<(unsigned)grid, 512, lds, s>>>(a, lda, b1, ldb1, b2, ldb2, k1, M, slab, ld_slab, pro);
   return grid;
 }
 
@@ -1550,7 +1709,7 @@ template <int NV, int KV, bool PRO = false>
 int64_t launch_wsd(const float* a, int64_t lda, const float* b1, int64_t ldb1, const float* b2, int64_t ldb2,
                    int64_t k1, int64_t M, float* slab, int64_t ld_slab, int64_t grid, hipStream_t s,
                    const WsdPro& pro = WsdPro{}) {
-  constexpr bool nt = true;   // non-temporal DMA of the streamed rows (1-3 % faster, profiles/r02/gemm_ws_bf16.txt)
+  // (the streamed rows are DMA'd non-temporal: 1-3 % faster, profiles/r02/gemm_ws_bf16.txt)
   if constexpr (NV == 256 && KV == 256) {   // the GIN width: the pipelined form (k_wsd_f32 measured 3-8 % slower
     auto kp = k_wsp_f32<PRO>;                 // here, profiles/r04/gpu_a/; removed from this shape in round 5)
     constexpr int plds = WspF32Cfg::lds<PRO>();
@@ -1558,7 +1717,7 @@ int64_t launch_wsd(const float* a, int64_t lda, const float* b1, int64_t ldb1, c
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, plds);
     if (pattr != hipSuccess) return 0;
     HGIN_TRACE("k_wsp_f32<%d,%d%s>", NV, KV, PRO ? ",prelu_bwd_fused" : "");
-    kp<<<(unsigned)grid, 512, plds, s>>>(a, lda, b1, ldb1, b2, ldb2, k1, M, slab, ld_slab, nt, pro);
+    kp<<<(unsigned)grid, 512, plds, s>>>(a, lda, b1, ldb1, b2, ldb2, k1, M, slab, ld_slab, pro);
     return grid;
   } else {
     constexpr int lds = WsdF32Cfg<NV, KV, PRO>::LDS;
@@ -1567,7 +1726,7 @@ int64_t launch_wsd(const float* a, int64_t lda, const float* b1, int64_t ldb1, c
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (attr != hipSuccess) return 0;
     HGIN_TRACE("k_wsd_f32<%d,%d%s>", NV, KV, PRO ? ",prelu_bwd_fused" : "");
-    kern<<<(unsigned)grid, 512, lds, s>>>(a, lda, b1, ldb1, b2, ldb2, k1, M, slab, ld_slab, nt, pro);
+    kern<<<(unsigned)grid, 512, lds, s>>>(a, lda, b1, ldb1, b2, ldb2, k1, M, slab, ld_slab, pro);
     return grid;
   }
 }

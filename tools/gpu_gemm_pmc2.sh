@@ -10,6 +10,8 @@ OUT=${OUT:-gpurun_out/gemm_pmc2}; mkdir -p "$OUT"; export TMPDIR=/tmp
 GROUPS_=("SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU"
          "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_INSTS_SALU"
          "GRBM_GUI_ACTIVE GRBM_COUNT")
+# PMC_GROUPS="A B C;D E" replaces the counter groups (one pass per ';'-separated group)
+if [ -n "${PMC_GROUPS:-}" ]; then IFS=';' read -r -a GROUPS_ <<< "$PMC_GROUPS"; fi
 # shape:HGIN_WSD_PIPE:HGIN_WS_PIPE
 for v in ${VARIANTS:-"fwd256:1:0" "fwd256:1:1" "dw256pro:0:0" "dw256pro:1:0"}; do
   IFS=: read -r shape wsd ws <<< "$v"
