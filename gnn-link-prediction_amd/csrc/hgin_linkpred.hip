@@ -130,6 +130,349 @@ __global__ __launch_bounds__(256) void k_dot_bwd(const int32_t* __restrict__ row
   }
 }
 
+// ---- A13 / A14: fused sampled link loss and ranking -------------------------------------------------------------
+// One G-lane group per positive edge e.  The group holds the source row in registers (ONE: the row fits one VEC-wide
+// piece per lane; otherwise the general loop re-reads it from cache), and scores pair t = 0 (the positive) and
+// t = 1..k (the negatives, destination regenerated from Philox counter offset + e * k + t - 1) against it, kInFlight
+// destination rows per batch so that several random-row loads are outstanding per wave.
+constexpr int kInFlight = 4;
+constexpr int kLinkMaxGrid = 4096;   // persistent grid: the per-block loss partials stay few and in a fixed order
+
+template <int VEC>
+__device__ __forceinline__ void ld_piece(const float* p, float (&v)[VEC]) {
+  if constexpr (VEC == 4) {
+    const float4 x = *reinterpret_cast<const float4*>(p);
+    v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+  } else {
+    v[0] = p[0];
+  }
+}
+
+template <int VEC>
+__device__ __forceinline__ float dot_piece(float acc, const float (&a)[VEC], const float (&b)[VEC]) {
+#pragma unroll
+  for (int c = 0; c < VEC; ++c) acc = __fadd_rn(acc, __fmul_rn(a[c], b[c]));
+  return acc;
+}
+
+template <int VEC>
+__device__ __forceinline__ void axpy_piece(float (&acc)[VEC], float w, const float (&x)[VEC]) {
+#pragma unroll
+  for (int c = 0; c < VEC; ++c) acc[c] = __fadd_rn(acc[c], __fmul_rn(w, x[c]));
+}
+
+// The same step with Kahan's compensation (same item order, still no FMA): the destination side uses it because a
+// destination's pair count E (1 + k) / n_dst has no bound (few destinations: thousands of terms that largely cancel),
+// where a plain fp32 running sum loses sqrt(n) eps of its largest partial sum.
+template <int VEC>
+__device__ __forceinline__ void axpy_comp_piece(float (&acc)[VEC], float (&comp)[VEC], float w, const float (&x)[VEC]) {
+#pragma unroll
+  for (int c = 0; c < VEC; ++c) {
+    const float y = __fsub_rn(__fmul_rn(w, x[c]), comp[c]);
+    const float t = __fadd_rn(acc[c], y);
+    comp[c] = __fsub_rn(__fsub_rn(t, acc[c]), y);
+    acc[c] = t;
+  }
+}
+
+template <int VEC>
+__device__ __forceinline__ void st_piece(float* p, const float (&v)[VEC]) {
+  if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  else p[0] = v[0];
+}
+
+__device__ __forceinline__ uint32_t word_of(const U4& x, uint32_t w) {
+  return w == 0 ? x.x : (w == 1 ? x.y : (w == 2 ? x.z : x.w));
+}
+
+template <int VEC, int G, bool ONE, bool RANK>
+__global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ pos, int64_t E, int k, uint64_t seed,
+                                                  uint64_t offset, uint32_t n_dst, const float* __restrict__ zs,
+                                                  int64_t lds, const float* __restrict__ zd, int64_t ldd, int F,
+                                                  float w_pos, float w_neg, float* __restrict__ coef,
+                                                  int64_t* __restrict__ neg, float* __restrict__ partial,
+                                                  int32_t* __restrict__ n_gt, int32_t* __restrict__ n_eq) {
+  constexpr int EPW = 64 / G;   // edges per wave
+  const int lane = threadIdx.x & 63;
+  const int grp = lane / G, gl = lane % G;
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  const int64_t n_waves = (int64_t)gridDim.x * 4;
+  const int64_t nk = E * (int64_t)k;
+  const bool lane_has = gl * VEC < F;   // ONE: this lane holds a piece of the row
+  float lsum = 0.0f;
+  for (int64_t wv = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); wv * EPW < E; wv += n_waves) {
+    const int64_t e_raw = wv * EPW + grp;
+    const bool valid = e_raw < E;
+    const int64_t e = valid ? e_raw : E - 1;   // idle groups redo the last edge (no divergence around the shuffles)
+    const bool writer = valid && gl == 0;
+    const int64_t d0 = pos[E + e];
+    const int64_t s0 = pos[e];
+    const float* a = zs + s0 * lds;
+    // pair t's loss term, coefficient and (t >= 1) drawn pair; e = exp(-|s|) serves softplus and sigmoid alike
+    auto finish_pair = [&](int t, float s, int64_t idm) {
+      const float ex = expf(-fabsf(s));
+      // sigmoid(s) for a negative, sigmoid(-s) = 1 - sigmoid(s) for the positive (no cancellation near 1)
+      const float sig = ((s >= 0.0f) != (t == 0) ? 1.0f : ex) / (1.0f + ex);
+      const float w = t == 0 ? w_pos : w_neg;
+      const float sp = __fadd_rn(fmaxf(t == 0 ? -s : s, 0.0f), log1pf(ex));   // softplus(-s) / softplus(s)
+      lsum = __fadd_rn(lsum, __fmul_rn(w, sp));
+      if (t == 0) {
+        coef[e] = __fmul_rn(w, -sig);
+      } else {
+        const int64_t q = e * (int64_t)k + (t - 1);
+        coef[E + q] = __fmul_rn(w, sig);
+        neg[q] = s0;
+        neg[nk + q] = idm;
+      }
+    };
+    float av[VEC];
+#pragma unroll
+    for (int c = 0; c < VEC; ++c) av[c] = 0.0f;
+    if (ONE && lane_has) ld_piece<VEC>(a + gl * VEC, av);
+    const uint64_t base = offset + (uint64_t)e * (uint64_t)k;
+    float s_pos = 0.0f;
+    int gt = 0, eq = 0;
+    for (int t0 = 0; t0 <= k; t0 += kInFlight) {
+      // destination ids of pairs t0 .. t0 + 3: their counters span at most two Philox blocks
+      const int tf = t0 == 0 ? 1 : t0;                       // first negative of the batch (tf <= k)
+      const int tl = t0 + kInFlight - 1 < k ? t0 + kInFlight - 1 : k;
+      const uint64_t c_first = base + (uint64_t)(tf - 1);
+      const uint64_t b0 = c_first >> 2;
+      const U4 X = philox4x32_10(U4{(uint32_t)b0, (uint32_t)(b0 >> 32), 0u, 0u}, k0, k1);
+      U4 Y = X;
+      if ((int)(c_first & 3) + (tl - tf) >= 4) {
+        const uint64_t b1 = b0 + 1;
+        Y = philox4x32_10(U4{(uint32_t)b1, (uint32_t)(b1 >> 32), 0u, 0u}, k0, k1);
+      }
+      int64_t id[kInFlight];
+#pragma unroll
+      for (int u = 0; u < kInFlight; ++u) {
+        const int t = t0 + u;
+        id[u] = d0;
+        if (t >= 1 && t <= k) {
+          const uint64_t c = base + (uint64_t)(t - 1);
+          const uint32_t wx = word_of(X, (uint32_t)c & 3u), wy = word_of(Y, (uint32_t)c & 3u);
+          const uint32_t r = (c >> 2) == b0 ? wx : wy;
+          id[u] = reduce_range(r, n_dst);
+        }
+      }
+      float sc[kInFlight];
+#pragma unroll
+      for (int u = 0; u < kInFlight; ++u) sc[u] = 0.0f;
+      if (ONE) {
+        float bv[kInFlight][VEC];
+#pragma unroll
+        for (int u = 0; u < kInFlight; ++u) {
+#pragma unroll
+          for (int c = 0; c < VEC; ++c) bv[u][c] = 0.0f;
+          if (lane_has && t0 + u <= k) ld_piece<VEC>(zd + id[u] * ldd + gl * VEC, bv[u]);   // t0, k uniform
+        }
+#pragma unroll
+        for (int u = 0; u < kInFlight; ++u) sc[u] = dot_piece<VEC>(sc[u], av, bv[u]);
+      } else {
+        for (int f = gl * VEC; f < F; f += G * VEC) {
+          float x[VEC], bv[kInFlight][VEC];
+          ld_piece<VEC>(a + f, x);
+#pragma unroll
+          for (int u = 0; u < kInFlight; ++u) {
+#pragma unroll
+            for (int c = 0; c < VEC; ++c) bv[u][c] = 0.0f;
+            if (t0 + u <= k) ld_piece<VEC>(zd + id[u] * ldd + f, bv[u]);
+          }
+#pragma unroll
+          for (int u = 0; u < kInFlight; ++u) sc[u] = dot_piece<VEC>(sc[u], x, bv[u]);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kInFlight; ++u) {
+#pragma unroll
+        for (int off = G / 2; off > 0; off >>= 1) sc[u] = __fadd_rn(sc[u], __shfl_xor(sc[u], off, G));
+      }
+      if constexpr (RANK) {
+#pragma unroll
+        for (int u = 0; u < kInFlight; ++u) {
+          const int t = t0 + u;
+          if (t == 0) s_pos = sc[u];
+          else if (t <= k) { gt += sc[u] > s_pos; eq += sc[u] == s_pos; }
+        }
+      } else if constexpr (G >= kInFlight) {
+        // every lane holds the four scores: lane u of the group finishes pair t0 + u (one exp / log1p per batch
+        // instead of four in a row on lane 0, and the group's stores fall side by side)
+        float s = sc[0];
+        int64_t idm = id[0];
+#pragma unroll
+        for (int u = 1; u < kInFlight; ++u)
+          if (gl == u) { s = sc[u]; idm = id[u]; }
+        if (valid && gl < kInFlight && t0 + gl <= k) finish_pair(t0 + gl, s, idm);
+      } else {
+#pragma unroll
+        for (int u = 0; u < kInFlight; ++u)
+          if (writer && t0 + u <= k) finish_pair(t0 + u, sc[u], id[u]);
+      }
+    }
+    if (RANK && writer) {
+      n_gt[e] = gt;
+      n_eq[e] = eq;
+    }
+  }
+  if (!RANK) {
+    // block partial in a fixed order: xor-tree inside the wave, then the four waves in order
+    __shared__ float wsum[4];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) lsum = __fadd_rn(lsum, __shfl_xor(lsum, off, 64));
+    if (lane == 0) wsum[threadIdx.x >> 6] = lsum;
+    __syncthreads();
+    if (threadIdx.x == 0)
+      partial[blockIdx.x] = __fadd_rn(__fadd_rn(__fadd_rn(wsum[0], wsum[1]), wsum[2]), wsum[3]);
+  }
+}
+
+// loss[0] = the partials added in a fixed order: thread i takes i, i + 256, ... in order, then a 256-wide tree
+__global__ __launch_bounds__(256) void k_link_loss_sum(const float* __restrict__ partial, int n,
+                                                       float* __restrict__ loss) {
+  __shared__ float sh[256];
+  float acc = 0.0f;
+  for (int i = threadIdx.x; i < n; i += 256) acc = __fadd_rn(acc, partial[i]);
+  sh[threadIdx.x] = acc;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) sh[threadIdx.x] = __fadd_rn(sh[threadIdx.x], sh[threadIdx.x + off]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss[0] = sh[0];
+}
+
+// Source-side gradient: a group per source row over the static CSC of the positives (rowptr / col = dst / perm =
+// edge id).  Items of the row in order: for each of its positives in CSC order, t = 0 (the positive's destination)
+// then its k negatives; acc += (g * c) * z_dst[id], kInFlight rows loaded per batch, added in item order.
+template <int VEC, int G>
+__global__ __launch_bounds__(256) void k_link_bwd_src(const int32_t* __restrict__ rowptr,
+                                                      const int32_t* __restrict__ col,
+                                                      const int32_t* __restrict__ perm, int64_t n_rows, int64_t E,
+                                                      int k, const float* __restrict__ g,
+                                                      const float* __restrict__ coef,
+                                                      const int64_t* __restrict__ neg_dst,
+                                                      const float* __restrict__ zd, int64_t ldd, int F,
+                                                      float* __restrict__ gz, int64_t ldg) {
+  const int lane = threadIdx.x & 63;
+  const int grp = lane / G, gl = lane % G;
+  const int64_t wave_id = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t r = wave_id * (64 / G) + grp;
+  if (r >= n_rows) return;
+  const float gv = g[0];
+  const int beg = rowptr[r], end = rowptr[r + 1];
+  const int64_t n_items = (int64_t)(end - beg) * (k + 1);
+  for (int f = gl * VEC; f < F; f += G * VEC) {
+    float acc[VEC];
+#pragma unroll
+    for (int c = 0; c < VEC; ++c) acc[c] = 0.0f;
+    int p = beg, t = 0;
+    // ids and weights of items i .. i + 3, branch-free so that each level of the index chain (perm / col, then the
+    // drawn id and the coefficient) is one batch of independent loads; items past the end repeat the last one
+    auto fetch = [&](int64_t i, int64_t (&id)[kInFlight], float (&w)[kInFlight]) {
+      int pu[kInFlight], tu[kInFlight];
+#pragma unroll
+      for (int u = 0; u < kInFlight; ++u) {
+        pu[u] = p;
+        tu[u] = t;
+        if (i + u < n_items - 1) {
+          if (++t > k) { t = 0; ++p; }
+        }
+      }
+      int32_t ev[kInFlight], cv[kInFlight];
+#pragma unroll
+      for (int u = 0; u < kInFlight; ++u) {
+        ev[u] = perm[pu[u]];
+        cv[u] = col[pu[u]];
+      }
+      int64_t q[kInFlight], nd[kInFlight];
+#pragma unroll
+      for (int u = 0; u < kInFlight; ++u) {
+        q[u] = (int64_t)ev[u] * k + (tu[u] > 0 ? tu[u] - 1 : 0);
+        nd[u] = neg_dst[q[u]];
+      }
+#pragma unroll
+      for (int u = 0; u < kInFlight; ++u) {
+        w[u] = __fmul_rn(gv, coef[tu[u] == 0 ? (int64_t)ev[u] : E + q[u]]);
+        id[u] = tu[u] == 0 ? (int64_t)cv[u] : nd[u];
+      }
+    };
+    for (int64_t i = 0; i < n_items; i += kInFlight) {
+      int64_t id[kInFlight];
+      float w[kInFlight];
+      fetch(i, id, w);
+      float x[kInFlight][VEC];
+#pragma unroll
+      for (int u = 0; u < kInFlight; ++u) ld_piece<VEC>(zd + id[u] * ldd + f, x[u]);
+#pragma unroll
+      for (int u = 0; u < kInFlight; ++u)
+        if (i + u < n_items) axpy_piece<VEC>(acc, w[u], x[u]);
+    }
+    st_piece<VEC>(gz + r * ldg + f, acc);
+  }
+}
+
+// Destination-side gradient: a group per destination row; items in order: the row's positives (static CSR of pos:
+// prow / pcol = src / pperm = edge id), then the row's negatives of this step (stable CSR of the drawn pairs by
+// destination: nrow / ncol = src / nperm = index e * k + j); acc += (g * c) * z_src[src], compensated (Kahan).
+template <int VEC, int G>
+__global__ __launch_bounds__(256) void k_link_bwd_dst(const int32_t* __restrict__ prow,
+                                                      const int32_t* __restrict__ pcol,
+                                                      const int32_t* __restrict__ pperm,
+                                                      const int32_t* __restrict__ nrow,
+                                                      const int32_t* __restrict__ ncol,
+                                                      const int32_t* __restrict__ nperm, int64_t n_rows, int64_t E,
+                                                      const float* __restrict__ g, const float* __restrict__ coef,
+                                                      const float* __restrict__ zs, int64_t lds, int F,
+                                                      float* __restrict__ gz, int64_t ldg) {
+  const int lane = threadIdx.x & 63;
+  const int grp = lane / G, gl = lane % G;
+  const int64_t wave_id = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t r = wave_id * (64 / G) + grp;
+  if (r >= n_rows) return;
+  const float gv = g[0];
+  const int pbeg = prow[r], nbeg = nrow[r];
+  const int n1 = prow[r + 1] - pbeg;
+  const int64_t n_items = (int64_t)n1 + (nrow[r + 1] - nbeg);
+  for (int f = gl * VEC; f < F; f += G * VEC) {
+    float acc[VEC], comp[VEC];
+#pragma unroll
+    for (int c = 0; c < VEC; ++c) acc[c] = comp[c] = 0.0f;
+    // ids and weights of items i .. i + 3, branch-free (the positive / negative arrays chosen by pointer selects)
+    // so that the index loads of a batch are independent; items past the end repeat the last one
+    auto fetch = [&](int64_t i, int64_t (&id)[kInFlight], float (&w)[kInFlight]) {
+      int32_t pm[kInFlight];
+      int64_t cb[kInFlight];
+#pragma unroll
+      for (int u = 0; u < kInFlight; ++u) {
+        const int64_t it = i + u < n_items ? i + u : n_items - 1;
+        const bool is_pos = it < n1;
+        const int32_t* cp = is_pos ? pcol : ncol;
+        const int32_t* pp = is_pos ? pperm : nperm;
+        const int64_t off = is_pos ? pbeg + it : nbeg + (it - n1);
+        id[u] = cp[off];
+        pm[u] = pp[off];
+        cb[u] = is_pos ? 0 : E;
+      }
+#pragma unroll
+      for (int u = 0; u < kInFlight; ++u) w[u] = __fmul_rn(gv, coef[cb[u] + pm[u]]);
+    };
+    for (int64_t i = 0; i < n_items; i += kInFlight) {
+      int64_t id[kInFlight];
+      float w[kInFlight];
+      fetch(i, id, w);
+      float x[kInFlight][VEC];
+#pragma unroll
+      for (int u = 0; u < kInFlight; ++u) ld_piece<VEC>(zs + id[u] * lds + f, x[u]);
+#pragma unroll
+      for (int u = 0; u < kInFlight; ++u)
+        if (i + u < n_items) axpy_comp_piece<VEC>(acc, comp, w[u], x[u]);
+    }
+    st_piece<VEC>(gz + r * ldg + f, acc);
+  }
+}
+
+
 int pick_g(int64_t lanes) {
   int g = 1;
   while (g < lanes && g < 64) g <<= 1;
@@ -206,4 +549,167 @@ extern "C" int hgin_dot_decode_bwd_f32(const int32_t* rowptr, const int32_t* col
                                                           (int)F, g_z, ld_g))
   }
   return check_launch("hgin_dot_decode_bwd_f32");
+}
+
+// ---- A13 / A14 entry points ---------------------------------------------------------------------------------------
+namespace {
+
+struct LinkShape {
+  bool vec;
+  int g;
+  bool one;
+  unsigned grid;
+};
+
+LinkShape link_shape(int64_t E, int64_t F, const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst) {
+  LinkShape s;
+  s.vec = F % 4 == 0 && aligned16(z_src) && aligned16(z_dst) && ld_src % 4 == 0 && ld_dst % 4 == 0;
+  const int64_t pieces = s.vec ? F / 4 : F;
+  s.one = pieces <= 64;
+  s.g = s.one ? pick_g(pieces) : 64;
+  const int64_t blocks = ceil_div(ceil_div(E, 64 / s.g), 4);
+  s.grid = (unsigned)(blocks < kLinkMaxGrid ? blocks : kLinkMaxGrid);
+  return s;
+}
+
+int link_common_checks(const char* what, const int64_t* pos, int64_t E, int64_t k, int64_t n_dst, const float* z_src,
+                       int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F) {
+  HGIN_ARG_CHECK(E >= 1 && E < (int64_t(1) << 31), "%s: E = %lld must be in [1, 2^31)", what, (long long)E);
+  HGIN_ARG_CHECK(k >= 1 && k < (int64_t(1) << 31), "%s: k = %lld must be >= 1", what, (long long)k);
+  HGIN_ARG_CHECK(E * k < (int64_t(1) << 31), "%s: E * k = %lld must be < 2^31", what, (long long)(E * k));
+  HGIN_ARG_CHECK(n_dst >= 1 && n_dst < (int64_t(1) << 31), "%s: n_dst must be in [1, 2^31)", what);
+  HGIN_ARG_CHECK(F >= 1 && F < (1 << 24), "%s: F must be in [1, 2^24)", what);
+  HGIN_ARG_CHECK(pos != nullptr, "%s: pos NULL", what);
+  HGIN_ARG_CHECK(z_src != nullptr, "%s: z_src NULL", what);
+  HGIN_ARG_CHECK(z_dst != nullptr, "%s: z_dst NULL", what);
+  HGIN_ARG_CHECK(ld_src >= F && ld_dst >= F, "%s: leading dimension too small", what);
+  return HGIN_OK;
+}
+
+template <bool RANK>
+void launch_link_fwd(const LinkShape& sh, hipStream_t s, const int64_t* pos, int64_t E, int k, uint64_t seed,
+                     uint64_t offset, uint32_t n_dst, const float* z_src, int64_t ld_src, const float* z_dst,
+                     int64_t ld_dst, int F, float* coef, int64_t* neg, float* partial, int32_t* n_gt, int32_t* n_eq) {
+  const float w_pos = (float)(0.5 / (double)E), w_neg = (float)(0.5 / ((double)E * (double)k));
+  HGIN_TRACE("k_link_fwd<%d,%d,%s,%s>", sh.vec ? 4 : 1, sh.g, sh.one ? "ONE" : "LOOP", RANK ? "RANK" : "LOSS");
+#define HGIN_LINK_FWD(VEC_, G_, ONE_)                                                                              \
+  k_link_fwd<VEC_, G_, ONE_, RANK><<<sh.grid, 256, 0, s>>>(pos, E, k, seed, offset, n_dst, z_src, ld_src, z_dst,   \
+                                                           ld_dst, F, w_pos, w_neg, coef, neg, partial, n_gt, n_eq)
+  if (sh.vec) {
+    if (!sh.one) HGIN_LINK_FWD(4, 64, false);
+    else HGIN_G_SWITCH(sh.g, HGIN_LINK_FWD(4, G, true))
+  } else {
+    if (!sh.one) HGIN_LINK_FWD(1, 64, false);
+    else HGIN_G_SWITCH(sh.g, HGIN_LINK_FWD(1, G, true))
+  }
+#undef HGIN_LINK_FWD
+}
+
+}  // namespace
+
+extern "C" int hgin_link_loss_workspace_size(int64_t n_pos, size_t* bytes) {
+  HGIN_ARG_CHECK(bytes != nullptr, "hgin_link_loss_workspace_size: bytes is NULL");
+  HGIN_ARG_CHECK(n_pos >= 1 && n_pos < (int64_t(1) << 31), "hgin_link_loss_workspace_size: E out of range");
+  *bytes = (size_t)kLinkMaxGrid * sizeof(float);
+  return HGIN_OK;
+}
+
+extern "C" int hgin_link_loss_fwd_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64_t seed, uint64_t offset,
+                                      int64_t n_dst, const float* z_src, int64_t ld_src, const float* z_dst,
+                                      int64_t ld_dst, int64_t F, float* coef, int64_t* neg, float* loss,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+  const int rc = link_common_checks("hgin_link_loss_fwd_f32", pos, n_pos, k, n_dst, z_src, ld_src, z_dst, ld_dst, F);
+  if (rc != HGIN_OK) return rc;
+  HGIN_ARG_CHECK(coef != nullptr, "hgin_link_loss_fwd_f32: coef NULL");
+  HGIN_ARG_CHECK(neg != nullptr, "hgin_link_loss_fwd_f32: neg NULL");
+  HGIN_ARG_CHECK(loss != nullptr, "hgin_link_loss_fwd_f32: loss NULL");
+  if (workspace == nullptr || workspace_bytes < (size_t)kLinkMaxGrid * sizeof(float)) {
+    set_error("hgin_link_loss_fwd_f32: workspace %zu bytes < required %zu", workspace_bytes,
+              (size_t)kLinkMaxGrid * sizeof(float));
+    return HGIN_E_WORKSPACE;
+  }
+  hipStream_t s = as_stream(stream);
+  const LinkShape sh = link_shape(n_pos, F, z_src, ld_src, z_dst, ld_dst);
+  float* partial = static_cast<float*>(workspace);
+  launch_link_fwd<false>(sh, s, pos, n_pos, (int)k, seed, offset, (uint32_t)n_dst, z_src, ld_src, z_dst, ld_dst,
+                         (int)F, coef, neg, partial, nullptr, nullptr);
+  int rc2 = check_launch("hgin_link_loss_fwd_f32");
+  if (rc2 != HGIN_OK) return rc2;
+  HGIN_TRACE("k_link_loss_sum");
+  k_link_loss_sum<<<1, 256, 0, s>>>(partial, (int)sh.grid, loss);
+  return check_launch("hgin_link_loss_fwd_f32");
+}
+
+extern "C" int hgin_link_rank_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64_t seed, uint64_t offset,
+                                  int64_t n_dst, const float* z_src, int64_t ld_src, const float* z_dst,
+                                  int64_t ld_dst, int64_t F, int32_t* n_greater, int32_t* n_equal, void* stream) {
+  const int rc = link_common_checks("hgin_link_rank_f32", pos, n_pos, k, n_dst, z_src, ld_src, z_dst, ld_dst, F);
+  if (rc != HGIN_OK) return rc;
+  HGIN_ARG_CHECK(n_greater != nullptr, "hgin_link_rank_f32: n_greater NULL");
+  HGIN_ARG_CHECK(n_equal != nullptr, "hgin_link_rank_f32: n_equal NULL");
+  const LinkShape sh = link_shape(n_pos, F, z_src, ld_src, z_dst, ld_dst);
+  launch_link_fwd<true>(sh, as_stream(stream), pos, n_pos, (int)k, seed, offset, (uint32_t)n_dst, z_src, ld_src, z_dst,
+                        ld_dst, (int)F, nullptr, nullptr, nullptr, n_greater, n_equal);
+  return check_launch("hgin_link_rank_f32");
+}
+
+extern "C" int hgin_link_loss_bwd_src_f32(const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                                          int64_t n_src, int64_t n_pos, int64_t k, const float* g, const float* coef,
+                                          const int64_t* neg, const float* z_dst, int64_t ld_dst, int64_t F,
+                                          float* g_src, int64_t ld_g, void* stream) {
+  const char* what = "hgin_link_loss_bwd_src_f32";
+  HGIN_ARG_CHECK(n_pos >= 1 && n_pos < (int64_t(1) << 31), "%s: E must be in [1, 2^31)", what);
+  HGIN_ARG_CHECK(k >= 1 && k < (int64_t(1) << 31) && n_pos * k < (int64_t(1) << 31),
+                 "%s: k must be >= 1 and E * k < 2^31", what);
+  HGIN_ARG_CHECK(n_src >= 1 && n_src < (int64_t(1) << 31), "%s: n_src must be in [1, 2^31)", what);
+  HGIN_ARG_CHECK(F >= 1 && F < (1 << 24), "%s: F must be in [1, 2^24)", what);
+  HGIN_ARG_CHECK(rowptr && col && perm, "%s: rowptr / col / perm NULL", what);
+  HGIN_ARG_CHECK(g && coef && neg, "%s: g / coef / neg NULL", what);
+  HGIN_ARG_CHECK(z_dst && g_src, "%s: z_dst / g_src NULL", what);
+  HGIN_ARG_CHECK(ld_dst >= F && ld_g >= F, "%s: leading dimension too small", what);
+  hipStream_t s = as_stream(stream);
+  const bool vec = F % 4 == 0 && aligned16(z_dst) && aligned16(g_src) && ld_dst % 4 == 0 && ld_g % 4 == 0;
+  const int gsz = pick_g(vec ? ceil_div(F, 4) : F);
+  const unsigned grid = (unsigned)ceil_div(ceil_div(n_src, 64 / gsz), 4);
+  const int64_t* neg_dst = neg + n_pos * k;
+  HGIN_TRACE("k_link_bwd_src<%d,%d>", vec ? 4 : 1, gsz);
+  if (vec) {
+    HGIN_G_SWITCH(gsz, k_link_bwd_src<4, G><<<grid, 256, 0, s>>>(rowptr, col, perm, n_src, n_pos, (int)k, g, coef,
+                                                                 neg_dst, z_dst, ld_dst, (int)F, g_src, ld_g))
+  } else {
+    HGIN_G_SWITCH(gsz, k_link_bwd_src<1, G><<<grid, 256, 0, s>>>(rowptr, col, perm, n_src, n_pos, (int)k, g, coef,
+                                                                 neg_dst, z_dst, ld_dst, (int)F, g_src, ld_g))
+  }
+  return check_launch(what);
+}
+
+extern "C" int hgin_link_loss_bwd_dst_f32(const int32_t* pos_rowptr, const int32_t* pos_col, const int32_t* pos_perm,
+                                          const int32_t* neg_rowptr, const int32_t* neg_col, const int32_t* neg_perm,
+                                          int64_t n_dst, int64_t n_pos, const float* g, const float* coef,
+                                          const float* z_src, int64_t ld_src, int64_t F, float* g_dst, int64_t ld_g,
+                                          void* stream) {
+  const char* what = "hgin_link_loss_bwd_dst_f32";
+  HGIN_ARG_CHECK(n_pos >= 1 && n_pos < (int64_t(1) << 31), "%s: E must be in [1, 2^31)", what);
+  HGIN_ARG_CHECK(n_dst >= 1 && n_dst < (int64_t(1) << 31), "%s: n_dst must be in [1, 2^31)", what);
+  HGIN_ARG_CHECK(F >= 1 && F < (1 << 24), "%s: F must be in [1, 2^24)", what);
+  HGIN_ARG_CHECK(pos_rowptr && pos_col && pos_perm, "%s: pos_rowptr / pos_col / pos_perm NULL", what);
+  HGIN_ARG_CHECK(neg_rowptr && neg_col && neg_perm, "%s: neg_rowptr / neg_col / neg_perm NULL", what);
+  HGIN_ARG_CHECK(g && coef, "%s: g / coef NULL", what);
+  HGIN_ARG_CHECK(z_src && g_dst, "%s: z_src / g_dst NULL", what);
+  HGIN_ARG_CHECK(ld_src >= F && ld_g >= F, "%s: leading dimension too small", what);
+  hipStream_t s = as_stream(stream);
+  const bool vec = F % 4 == 0 && aligned16(z_src) && aligned16(g_dst) && ld_src % 4 == 0 && ld_g % 4 == 0;
+  const int gsz = pick_g(vec ? ceil_div(F, 4) : F);
+  const unsigned grid = (unsigned)ceil_div(ceil_div(n_dst, 64 / gsz), 4);
+  HGIN_TRACE("k_link_bwd_dst<%d,%d>", vec ? 4 : 1, gsz);
+  if (vec) {
+    HGIN_G_SWITCH(gsz, k_link_bwd_dst<4, G><<<grid, 256, 0, s>>>(pos_rowptr, pos_col, pos_perm, neg_rowptr, neg_col,
+                                                                 neg_perm, n_dst, n_pos, g, coef, z_src, ld_src,
+                                                                 (int)F, g_dst, ld_g))
+  } else {
+    HGIN_G_SWITCH(gsz, k_link_bwd_dst<1, G><<<grid, 256, 0, s>>>(pos_rowptr, pos_col, pos_perm, neg_rowptr, neg_col,
+                                                                 neg_perm, n_dst, n_pos, g, coef, z_src, ld_src,
+                                                                 (int)F, g_dst, ld_g))
+  }
+  return check_launch(what);
 }

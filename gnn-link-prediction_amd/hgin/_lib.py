@@ -170,6 +170,12 @@ _SIGS = {
     "hgin_neg_sample": ([_U64, _U64, _I64, _I64, _P, _P], _I32),
     "hgin_dot_decode_fwd_f32": ([_P, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _P], _I32),
     "hgin_dot_decode_bwd_f32": ([_P, _P, _P, _I64, _P, _P, _I64, _I64, _P, _I64, _P], _I32),
+    "hgin_link_loss_workspace_size": ([_I64, ctypes.POINTER(_SZ)], _I32),
+    "hgin_link_loss_fwd_f32": ([_P, _I64, _I64, _U64, _U64, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _P, _P, _SZ, _P],
+                               _I32),
+    "hgin_link_loss_bwd_src_f32": ([_P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _P, _I64, _P], _I32),
+    "hgin_link_loss_bwd_dst_f32": ([_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _I64, _I64, _P, _I64, _P], _I32),
+    "hgin_link_rank_f32": ([_P, _I64, _I64, _U64, _U64, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _P], _I32),
     "hgin_aggregate_long_f32": ([_P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I32, _P, _I64, _P,
                                  _SZ, _P], _I32),
     "hgin_aggregate_long_bf16": ([_P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I32, _P, _I64, _P,
@@ -200,7 +206,7 @@ _SIGS = {
     "hgin_trace_enable": ([_I32], _I32),
     "hgin_trace_read": ([ctypes.c_char_p, _SZ], _SZ),
 }
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 def lib() -> ctypes.CDLL:

@@ -7,8 +7,16 @@ star asks for a negative-edge sampler and a dot-product link decoder as HIP kern
 Specs (include/hgin.h): sampler out[i] = hi32(philox4x32_10(block (offset+i)>>2)[(offset+i)&3] * n_dst);
 decoder score[e] = <z_src[src[e]], z_dst[dst[e]]>, backward = weighted segmented sums over the pairs'
 CSR / CSC (bit-exact against oracle/hgin_oracle.c).
+
+Training path (A13 / A14, also not in the reference): ``sampled_link_loss`` is ``link_loss`` as one fused forward
+(negatives regenerated in the kernel, source row read once, loss and coefficients in the same pass) with a
+deterministic store-and-sum backward; ``link_ranks`` / ``link_metrics`` evaluate with the same kernel and another
+epilogue; ``LinkPredictor`` puts them behind ``model.encode`` (hgin/train.py::link_train_step).  ``link_loss`` and
+the unfused pieces stay as the baseline the fused path is checked and timed against (tools/bench_linkpred.py).
 """
 from __future__ import annotations
+
+import ctypes
 
 import torch
 from torch import Tensor
@@ -87,3 +95,175 @@ def link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offs
     s_neg = dot_decode(z_src, z_dst, neg)
     bce = torch.nn.functional.binary_cross_entropy_with_logits
     return bce(s_pos, torch.ones_like(s_pos)) * 0.5 + bce(s_neg, torch.zeros_like(s_neg)) * 0.5
+
+
+# ---------------------------------------------------------------------------------------------------
+# A13 / A14: the fused sampled link loss, sampled ranks and the training head (NOT IN REFERENCE)
+# ---------------------------------------------------------------------------------------------------
+def _link_operands(what: str, z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int):
+    """Checked operands of the fused kernels: fp32 row-major embeddings of one width, validated positives."""
+    ops.require_device(z_src, z_dst, pos, what=what)
+    for name, z in (("z_src", z_src), ("z_dst", z_dst)):
+        if z.dtype != torch.float32:
+            raise TypeError(f"{what}: {name} must be float32 (the fused link kernels are fp32 only), got {z.dtype}")
+        if z.dim() != 2:
+            raise RuntimeError(f"{what}: {name} must be [N, F]")
+    if z_src.size(1) != z_dst.size(1):
+        raise RuntimeError(f"{what}: embedding widths differ")
+    ops.check_edge_index(pos)
+    E, k = int(pos.size(1)), int(k)
+    if E < 1 or k < 1 or E * k >= 2**31:
+        raise ValueError(f"{what}: need E >= 1, k >= 1 and E * k < 2^31 (E = {E}, k = {k})")
+    # the static CSR / CSC of the positives: built (and range-checked) once per pos tensor, cached on it
+    graph = ops.relation_graph(pos, z_src.size(0), z_dst.size(0))
+    return ops._rowmajor(z_src), ops._rowmajor(z_dst), pos.contiguous(), graph, E, k
+
+
+_SIDE_STREAMS: dict = {}
+
+
+def _side_stream(device) -> "torch.cuda.Stream":
+    """One extra stream per device for the per-step sort of the negatives (see _SampledLinkLossFn.backward)."""
+    key = torch.device(device).index if torch.device(device).index is not None else torch.cuda.current_device()
+    s = _SIDE_STREAMS.get(key)
+    if s is None:
+        s = _SIDE_STREAMS[key] = torch.cuda.Stream(device=key)
+    return s
+
+
+class _SampledLinkLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z_src, z_dst, pos, graph: ops.RelationGraph, k: int, seed: int, offset: int):
+        E, F, dev = int(pos.size(1)), int(z_src.size(1)), z_src.device
+        coef = torch.empty(E * (1 + k), dtype=torch.float32, device=dev)
+        neg = torch.empty((2, E * k), dtype=torch.int64, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        nbytes = ctypes.c_size_t(0)
+        _lib.check(_lib.lib().hgin_link_loss_workspace_size(E, ctypes.byref(nbytes)), "hgin_link_loss_workspace_size")
+        ws = ops._workspace(nbytes.value, dev)
+        _lib.call("hgin_link_loss_fwd_f32", ops._p(pos), E, k, int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
+                  int(z_dst.size(0)), ops._p(z_src), z_src.stride(0), ops._p(z_dst), z_dst.stride(0), F, ops._p(coef),
+                  ops._p(neg), ops._p(loss), ops._p(ws), nbytes.value, ops._stream(loss))
+        ctx.graph, ctx.k = graph, k
+        ctx.save_for_backward(coef, neg, z_src, z_dst)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        coef, neg, z_src, z_dst = ctx.saved_tensors
+        graph, k = ctx.graph, ctx.k
+        E, F, dev = graph.n_edges, int(z_src.size(1)), z_src.device
+        g = g.reshape(1).to(torch.float32).contiguous()   # device scalar: no host sync
+        g_src = g_dst = None
+        cur = torch.cuda.current_stream(dev)
+        side = None
+        if ctx.needs_input_grad[1]:
+            csr = graph.csr           # rows = dst, col = src (static)
+            n_dst, n_neg = int(z_dst.size(0)), E * k
+            # this step's negatives by destination: one stable sort, no validation sync (sources are the
+            # positives', destinations are < n_dst by construction).  Its buffers are allocated on the current
+            # stream; when the source side runs too, the sort (many short passes, far from the HBM rate) is issued on
+            # a side stream so that it overlaps the source-side gather, and the current stream waits for it below.
+            nrow = torch.empty(n_dst + 1, dtype=torch.int32, device=dev)
+            ncol = torch.empty(n_neg, dtype=torch.int32, device=dev)
+            nperm = torch.empty(n_neg, dtype=torch.int32, device=dev)
+            status = torch.zeros(1, dtype=torch.int32, device=dev)
+            nbytes = ctypes.c_size_t(0)
+            _lib.check(_lib.lib().hgin_csr_workspace_size(n_neg, n_dst, ctypes.byref(nbytes)),
+                       "hgin_csr_workspace_size")
+            ws = ops._workspace(nbytes.value, dev)
+            sort_stream = cur
+            if ctx.needs_input_grad[0]:
+                side = sort_stream = _side_stream(dev)
+                side.wait_stream(cur)
+            _lib.call("hgin_csr_build", ops._p(neg), n_neg, 1, n_dst, int(z_src.size(0)), ops._p(nrow), ops._p(ncol),
+                      ops._p(nperm), ops._p(status), ops._p(ws), nbytes.value, ctypes.c_void_p(sort_stream.cuda_stream))
+        if ctx.needs_input_grad[0]:
+            csc = graph.csc           # rows = src, col = dst (static)
+            g_src = torch.empty((z_src.size(0), F), dtype=torch.float32, device=dev)
+            _lib.call("hgin_link_loss_bwd_src_f32", ops._p(csc.rowptr), ops._p(csc.col), ops._p(csc.perm), csc.n_rows,
+                      E, k, ops._p(g), ops._p(coef), ops._p(neg), ops._p(z_dst), z_dst.stride(0), F, ops._p(g_src),
+                      g_src.stride(0), ops._stream(g))
+        if ctx.needs_input_grad[1]:
+            if side is not None:
+                cur.wait_stream(side)   # every later use (and reuse) of the sort's buffers is ordered after it
+            g_dst = torch.empty((n_dst, F), dtype=torch.float32, device=dev)
+            _lib.call("hgin_link_loss_bwd_dst_f32", ops._p(csr.rowptr), ops._p(csr.col), ops._p(csr.perm),
+                      ops._p(nrow), ops._p(ncol), ops._p(nperm), n_dst, E, ops._p(g), ops._p(coef), ops._p(z_src),
+                      z_src.stride(0), F, ops._p(g_dst), g_dst.stride(0), ops._stream(g))
+        return g_src, g_dst, None, None, None, None, None
+
+
+def sampled_link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0) -> Tensor:
+    """``link_loss`` in fused form (include/hgin.h A13): the same pairs (``negative_edges(pos, n_dst, k, seed,
+    offset)``) and the same loss, one forward pass that draws the negatives in the kernel and reads every source
+    row once, and a deterministic store-and-sum backward (static CSC / CSR of ``pos`` + one sort of the step's
+    negatives).  Returns a scalar; fp32 embeddings only."""
+    z_src, z_dst, pos, graph, _, k = _link_operands("sampled_link_loss", z_src, z_dst, pos, k)
+    return _SampledLinkLossFn.apply(z_src, z_dst, pos, graph, k, int(seed), int(offset))
+
+
+def link_ranks(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0):
+    """(n_greater, n_equal), int32 [E]: how many of each positive's k sampled negatives (the draws of
+    ``sampled_link_loss``) score above / exactly equal to it (include/hgin.h A14).  No gradient."""
+    z_src, z_dst, pos, _, E, k = _link_operands("link_ranks", z_src, z_dst, pos, k)
+    z_src, z_dst = z_src.detach(), z_dst.detach()
+    n_gt = torch.empty(E, dtype=torch.int32, device=z_src.device)
+    n_eq = torch.empty(E, dtype=torch.int32, device=z_src.device)
+    _lib.call("hgin_link_rank_f32", ops._p(pos), E, k, int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
+              int(z_dst.size(0)), ops._p(z_src), z_src.stride(0), ops._p(z_dst), z_dst.stride(0), int(z_src.size(1)),
+              ops._p(n_gt), ops._p(n_eq), ops._stream(n_gt))
+    return n_gt, n_eq
+
+
+def metrics_from_ranks(n_greater: Tensor, n_equal: Tensor, k: int) -> dict:
+    """Sampled ranking metrics as 0-dim tensors on the ranks' device (nothing is synchronised):
+    auc = 1 - (sum greater + 0.5 sum equal) / (E k); with rank = 1 + greater + equal / 2 (ties share the middle
+    rank): mrr = mean 1 / rank, hits@K = mean [rank <= K]."""
+    gt, eq = n_greater.to(torch.float64), n_equal.to(torch.float64)
+    E = gt.numel()
+    rank = 1.0 + gt + 0.5 * eq
+    out = {"auc": 1.0 - (gt.sum() + 0.5 * eq.sum()) / float(E * int(k)), "mrr": (1.0 / rank).mean()}
+    for K in (1, 3, 10):
+        out[f"hits@{K}"] = (rank <= K).to(torch.float64).mean()
+    return out
+
+
+def link_metrics(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0) -> dict:
+    """auc / mrr / hits@1 / hits@3 / hits@10 of the positives against k sampled negatives each, as device scalars
+    (float64): the ranking kernel + a few reductions over [E]; no host sync before the caller reads a value."""
+    n_gt, n_eq = link_ranks(z_src, z_dst, pos, k, seed, offset)
+    return metrics_from_ranks(n_gt, n_eq, k)
+
+
+class LinkPredictor:
+    """Link-prediction head over a model's node embeddings: ``relation`` = (src_type, name, dst_type), k uniform
+    negatives per positive, dot-product decoder, BCE-with-logits (``sampled_link_loss``)."""
+
+    def __init__(self, model, relation, k: int, seed: int):
+        if not hasattr(model, "encode"):
+            raise TypeError("LinkPredictor: the model has no encode(x_dict, edge_index_dict)")
+        self.model, self.relation, self.k, self.seed = model, tuple(relation), int(k), int(seed)
+
+    def _pos(self, graph, pos):
+        return graph.edge_index[self.relation] if pos is None else pos
+
+    def loss(self, graph, pos: Tensor = None, step: int = 0) -> Tensor:
+        """The sampled loss of ``pos`` (default: the relation's own edges); step s draws the negatives at
+        offset s * E * k, so every step sees fresh ones."""
+        pos = self._pos(graph, pos)
+        z = self.model.encode(graph.x_dict(), graph.edge_index_dict())
+        offset = int(step) * int(pos.size(1)) * self.k
+        return sampled_link_loss(z[self.relation[0]], z[self.relation[2]], pos, self.k, self.seed, offset)
+
+    def metrics(self, graph, pos: Tensor = None) -> dict:
+        """``link_metrics`` of the model's embeddings in eval mode, without gradients (the mode is restored)."""
+        pos = self._pos(graph, pos)
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                z = self.model.encode(graph.x_dict(), graph.edge_index_dict())
+                return link_metrics(z[self.relation[0]], z[self.relation[2]], pos, self.k, self.seed)
+        finally:
+            self.model.train(was_training)

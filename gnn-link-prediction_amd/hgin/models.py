@@ -209,19 +209,30 @@ class HetroGIN(torch.nn.Module):
         the loss covers path rows < m_valid (padded static-shape batches, hgin/graphs.py)."""
         return self._run(x_dict, edge_index_dict, path_batch, y, m_valid)
 
-    def _run(self, x_dict, edge_index_dict, path_batch, y, m_valid):
+    def encode(self, x_dict, edge_index_dict):
+        """Per-type node embeddings {type: [N_t, H]} (H * heads for HetroGAT): the feature slicing and the
+        ``num_layers`` conv loop of ``forward`` (with the model's dropout in training mode), without the path
+        read-out.  NOT IN REFERENCE (its ``forward`` only returns the read-out); the input of the link-prediction
+        head (hgin/linkpred.py).  Device tensors only; the caller's ``x_dict`` is left as it is."""
+        ops.require_device(*x_dict.values(), *edge_index_dict.values(), what="encode")
+        return self._embed(dict(x_dict), edge_index_dict)[0]
+
+    def _embed(self, x_dict, edge_index_dict):
+        """models.py:333-342 + :355-359: (embeddings per type, the sliced input features)."""
         self._select_features(x_dict)
         origin_input = x_dict.copy()
-
-        pooled = None
-        if self.global_feats:   # models.py:347-352: [mean | max] per graph, gathered to the rows, in one launch
-            pooled = ops.global_pool(origin_input["path"], path_batch)
-
         for i in range(self.num_layers):   # models.py:355-359
             x_dict = self.convs[i](x_dict, edge_index_dict)
             if self.dropout > 0.0 and self.training:
                 for k in list(x_dict.keys()):
                     x_dict[k] = torch.nn.functional.dropout(x_dict[k], p=self.dropout, training=True)
+        return x_dict, origin_input
+
+    def _run(self, x_dict, edge_index_dict, path_batch, y, m_valid):
+        x_dict, origin_input = self._embed(x_dict, edge_index_dict)
+        pooled = None
+        if self.global_feats:   # models.py:347-352: [mean | max] per graph, gathered to the rows, in one launch
+            pooled = ops.global_pool(origin_input["path"], path_batch)
         return self._readout(x_dict["path"], origin_input["path"], pooled, y, m_valid)
 
     def _select_features(self, x_dict):

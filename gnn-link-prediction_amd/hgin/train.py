@@ -36,6 +36,19 @@ def load_optimizer(config: dict, model: torch.nn.Module) -> torch.optim.Optimize
     raise ValueError(f"unknown optimizer {kind!r}")
 
 
+def link_train_step(model, opt, graph, predictor, step: int = 0) -> torch.Tensor:
+    """One link-prediction iteration (no reference counterpart): zero_grad, ``predictor.loss(graph, step=step)``
+    (``model.encode`` + the fused sampled link loss, fresh negatives per step), backward, ``opt.step()``.
+    ``predictor`` is a ``hgin.linkpred.LinkPredictor`` over ``model``.  Returns the detached device loss."""
+    if predictor.model is not model:
+        raise ValueError("link_train_step: the predictor was built over another model")
+    opt.zero_grad()
+    loss = predictor.loss(graph, step=step)
+    loss.backward()
+    opt.step()
+    return loss.detach()
+
+
 def train_step(model, opt, graph, loss_func=mape, reducer: Optional[GradAllReducer] = None,
                sync_metric: bool = False, fused_loss: bool = True):
     """One train.py:31-44 iteration.  ``fused_loss`` (default): when the loss is train.py's ``mape`` and the

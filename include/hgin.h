@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HGIN_ABI_VERSION 8
+#define HGIN_ABI_VERSION 9
 
 #define HGIN_OK 0
 #define HGIN_E_ARG (-1)        /* bad size / null pointer / unsupported combination */
@@ -407,6 +407,60 @@ int hgin_dot_decode_fwd_f32(const int32_t* src, const int32_t* dst, int64_t n_pa
 int hgin_dot_decode_bwd_f32(const int32_t* rowptr, const int32_t* col, const int32_t* perm,
                             int64_t n_rows, const float* g_score, const float* z_other,
                             int64_t ld_other, int64_t F, float* g_z, int64_t ld_g, void* stream);
+
+/* ---- A13: fused sampled link loss (NOT IN REFERENCE; build-defined, ABI 9) -------------------------------------
+ * The loss of A10 + A11 + BCE-with-logits in one pass, without materialising the negatives ahead of the scores.
+ * pos: int64 [2, E] (row 0 = source ids into z_src, row 1 = destination ids into z_dst; the caller guarantees the
+ * ranges, e.g. through hgin_csr_build's status).  For positive e and slot j < k the negative pair is
+ * (pos[0, e], draw(offset + e * k + j)) with draw = hgin_neg_sample's definition (Philox block c >> 2, word c & 3,
+ * multiply-shift into [0, n_dst)): the pairs hgin_neg_sample(seed, offset, E * k, n_dst) gives, sources repeated k
+ * times.  Scores s = <z_src[src], z_dst[dst]> (fp32, mul then add, lane pieces joined by an xor tree).
+ *   loss = 0.5 / E * sum_e softplus(-s_pos[e]) + 0.5 / (E k) * sum_{e, j} softplus(s_neg[e, j]),
+ *   softplus(x) = max(x, 0) + log1p(exp(-|x|)) with the accurate expf / log1pf.
+ * hgin_link_loss_fwd_f32 writes
+ *   coef  float [E + E k]: coef[e] = 0.5 / E * (sigmoid(s_pos[e]) - 1), coef[E + e k + j] = 0.5 / (E k) * sigmoid(s_neg),
+ *   neg   int64 [2, E k]:  the drawn pairs in hgin_csr_build's edge_index layout (row 0 sources, row 1 destinations),
+ *   loss  float [1].
+ *   (sigmoid(s) - 1 is formed as -sigmoid(-s), both from the one exp(-|s|) the softplus uses.)
+ * Summation order of the loss (fixed, no float atomics): a persistent grid of at most 4096 workgroups; a group
+ * takes its edges in order and their pairs t = 0 (positive), 1 .. k in batches of four; lane u < 4 of the group adds
+ * the terms of the pairs t = u mod 4 in that order (groups narrower than four lanes: lane 0 adds all of them in
+ * order); a workgroup joins its lanes by an xor tree per wave and adds its four waves in order into
+ * partial[workgroup] (workspace:
+ * hgin_link_loss_workspace_size); a second one-workgroup kernel adds the partials (thread i takes i, i + 256, ...
+ * in order, then a 256-wide tree) into loss[0].  Run-to-run bit-identical.
+ * Backward (g = device float [1], the upstream gradient of the loss; no host sync):
+ *   hgin_link_loss_bwd_src_f32: rowptr / col / perm = hgin_csr_build(pos, key_row = 0) (static: one sort per pos).
+ *     g_src[s] = sum over the row's positives in CSC order, and for each over t = 0 .. k in order, of
+ *     (g * coef) * z_dst[id] (mul, mul, add; no FMA); rows without positives get exact zeros.
+ *   hgin_link_loss_bwd_dst_f32: pos_* = hgin_csr_build(pos, key_row = 1) (static), neg_* = hgin_csr_build(neg,
+ *     key_row = 1) (this step's negatives, one stable sort per step).  g_dst[d] = the row's positives in CSR order,
+ *     then its negatives in CSR order (= ascending e k + j), each (g * coef) * z_src[src]; other rows exact zeros.
+ *     This running sum carries Kahan's compensation term (same order, mul / add / sub only): a destination's pair
+ *     count E (1 + k) / n_dst is unbounded, and with few destinations thousands of largely cancelling terms cost a
+ *     plain fp32 sum more than the 1e-5 the gradients are held to (measured 1.2e-5 at n_dst = 1, E = 211, k = 5).
+ * fp32 only.  E >= 1, k >= 1, E k < 2^31, 1 <= n_dst < 2^31, 1 <= F < 2^24: HGIN_E_ARG before any launch otherwise.
+ * Rows are walked serially per lane group (no long-row split): destinations with very many pairs serialise. */
+int hgin_link_loss_workspace_size(int64_t n_pos, size_t* bytes);
+int hgin_link_loss_fwd_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64_t seed, uint64_t offset,
+                           int64_t n_dst, const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst,
+                           int64_t F, float* coef, int64_t* neg, float* loss, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int hgin_link_loss_bwd_src_f32(const int32_t* rowptr, const int32_t* col, const int32_t* perm, int64_t n_src,
+                               int64_t n_pos, int64_t k, const float* g, const float* coef, const int64_t* neg,
+                               const float* z_dst, int64_t ld_dst, int64_t F, float* g_src, int64_t ld_g,
+                               void* stream);
+int hgin_link_loss_bwd_dst_f32(const int32_t* pos_rowptr, const int32_t* pos_col, const int32_t* pos_perm,
+                               const int32_t* neg_rowptr, const int32_t* neg_col, const int32_t* neg_perm,
+                               int64_t n_dst, int64_t n_pos, const float* g, const float* coef, const float* z_src,
+                               int64_t ld_src, int64_t F, float* g_dst, int64_t ld_g, void* stream);
+
+/* ---- A14: sampled ranking for evaluation (NOT IN REFERENCE; build-defined, ABI 9) ------------------------------
+ * The A13 forward with another epilogue: for every positive e, n_greater[e] / n_equal[e] (int32 [E]) = how many of
+ * its k sampled negatives (same draws as A13) score above / exactly equal to the positive.  Writes nothing else. */
+int hgin_link_rank_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64_t seed, uint64_t offset, int64_t n_dst,
+                       const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F,
+                       int32_t* n_greater, int32_t* n_equal, void* stream);
 
 /* ---- F4 widening: HetroGAT's graph attention (models.py:380-506, PyG 2.0.2 GATConv) ---------------------------
  * x_s / x_d: projected source / destination features [N, H * C] (row stride ld*), edges = the relation after

@@ -1,0 +1,189 @@
+#!/usr/bin/env python3
+"""Time the fused sampled link loss (A13) against the unfused ``link_loss`` (A10 + A11 + torch BCE), and the ranking
+kernel (A14), on one GPU in one process.
+
+Shapes: the ('path', 'uses', 'link') relation of CONFIGS[cfg] (n_path sources, n_link destinations, e_pl positives,
+F = the config's hidden width), k negatives per positive.  Both paths get identical inputs (same positives, same
+embeddings, same seed and offsets), run forward + backward, are warmed up per shape and alternate; every timed
+repeat is ``inner`` iterations between two HIP events (inner chosen from the warm-up so that a repeat is tens of
+milliseconds).  Reported per shape: median / min / max of the repeats for both paths, their ratio, whether the fused
+path is faster by more than the spread (its slowest repeat under link_loss's fastest), the fused forward alone with
+its algorithmic bytes and fraction of the 8 TB/s HBM peak, and the ranking kernel.  A path that runs out of memory is
+recorded as such.  There is no CPU fallback: without a HIP device the tool prints the plan and fails.
+
+    python tools/bench_linkpred.py --out profiles/linkpred/linkpred_bench.json
+    python tools/bench_linkpred.py --configs cfg1 --scale 0.1 --k 1      # a tiny run
+"""
+import argparse
+import json
+import math
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "gnn-link-prediction_amd")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+HBM_PEAK = 8.0e12          # bytes / s
+DECODER_HBM_FRACTION = 0.73   # the existing dot-product decoder's recorded fraction
+
+
+def fwd_algorithmic_bytes(E: int, k: int, F: int) -> int:
+    """Source rows once, destination rows once per pair, coefficient and negative-pair writes, index reads."""
+    rows = E * F * 4 + (1 + k) * E * F * 4
+    writes = (1 + k) * E * 4 + 2 * E * k * 8
+    index_reads = 2 * E * 8
+    return rows + writes + index_reads
+
+
+def rank_algorithmic_bytes(E: int, k: int, F: int) -> int:
+    return E * F * 4 + (1 + k) * E * F * 4 + 2 * E * 8 + 2 * E * 4
+
+
+def plan(configs, ks, scale: float):
+    from hgin.data import CONFIGS, scaled_config
+    shapes = []
+    for name in configs:
+        cfg = CONFIGS[name]
+        if scale != 1.0:
+            cfg = scaled_config(cfg, scale)
+        for k in ks:
+            E, F = cfg.e_pl, cfg.hidden
+            if E * k >= 2**31:
+                raise SystemExit(f"{name}: E * k = {E * k} does not fit the kernels' 2^31 limit")
+            shapes.append({"config": name, "scale": scale, "n_src": cfg.n_path, "n_dst": cfg.n_link, "E": E, "F": F,
+                           "k": k, "fwd_algorithmic_bytes": fwd_algorithmic_bytes(E, k, F),
+                           "rank_algorithmic_bytes": rank_algorithmic_bytes(E, k, F)})
+    return shapes
+
+
+def _stats(ms):
+    med = statistics.median(ms)
+    return {"median_ms": med, "min_ms": min(ms), "max_ms": max(ms), "spread": (max(ms) - min(ms)) / med,
+            "repeats_ms": ms}
+
+
+def _timed(torch, fn, inner, first_step):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for i in range(inner):
+        fn(first_step + i)
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / inner
+
+
+def _inner_for(torch, fn, target_ms):
+    fn(0)
+    torch.cuda.synchronize()
+    t = _timed(torch, fn, 1, 1)
+    return max(1, int(math.ceil(target_ms / max(t, 1e-3))))
+
+
+def run_shape(torch, shape, repeats, warmup, target_ms, seed=1234):
+    from hgin.linkpred import link_loss, link_ranks, sampled_link_loss
+    dev = "cuda"
+    n_src, n_dst, E, F, k = (shape[x] for x in ("n_src", "n_dst", "E", "F", "k"))
+    g = torch.Generator(device=dev).manual_seed(seed)
+    pos = torch.stack([torch.randint(0, n_src, (E,), generator=g, device=dev),
+                       torch.randint(0, n_dst, (E,), generator=g, device=dev)])
+    z_src = (torch.randn(n_src, F, generator=g, device=dev) * 0.1).requires_grad_(True)
+    z_dst = (torch.randn(n_dst, F, generator=g, device=dev) * 0.1).requires_grad_(True)
+
+    def step_of(loss_fn):
+        def fn(step):
+            z_src.grad = z_dst.grad = None
+            loss_fn(z_src, z_dst, pos, k, seed, step * E * k).backward()
+        return fn
+
+    def fwd_only(step):
+        with torch.no_grad():
+            sampled_link_loss(z_src, z_dst, pos, k, seed, step * E * k)
+
+    def rank_only(step):
+        link_ranks(z_src, z_dst, pos, k, seed, step * E * k)
+
+    fused, base = step_of(sampled_link_loss), step_of(link_loss)
+    out = dict(shape)
+    base_ok = True
+    try:
+        for s in range(warmup):
+            fused(s)
+            base(s)
+        torch.cuda.synchronize()
+    except torch.OutOfMemoryError:
+        base_ok = False
+        z_src.grad = z_dst.grad = None
+        torch.cuda.empty_cache()
+        for s in range(warmup):
+            fused(s)
+        torch.cuda.synchronize()
+    inner_f = _inner_for(torch, fused, target_ms)
+    inner_b = _inner_for(torch, base, target_ms) if base_ok else 0
+    t_f, t_b, step = [], [], warmup
+    for _ in range(repeats):      # the two paths alternate
+        t_f.append(_timed(torch, fused, inner_f, step))
+        if base_ok:
+            t_b.append(_timed(torch, base, inner_b, step))
+        step += max(inner_f, inner_b)
+    out["fused"] = dict(_stats(t_f), inner=inner_f)
+    if base_ok:
+        out["link_loss"] = dict(_stats(t_b), inner=inner_b)
+        out["link_loss_over_fused"] = out["link_loss"]["median_ms"] / out["fused"]["median_ms"]
+        out["fused_faster_beyond_spread"] = out["fused"]["max_ms"] < out["link_loss"]["min_ms"]
+    else:
+        out["link_loss"] = {"error": "out of memory"}
+    z_src.grad = z_dst.grad = None
+    for name, fn, nbytes in (("fused_forward", fwd_only, shape["fwd_algorithmic_bytes"]),
+                             ("rank", rank_only, shape["rank_algorithmic_bytes"])):
+        inner = _inner_for(torch, fn, target_ms)
+        st = _stats([_timed(torch, fn, inner, warmup + r * inner) for r in range(repeats)])
+        st.update(inner=inner, algorithmic_bytes=nbytes,
+                  hbm_fraction=nbytes / (st["median_ms"] * 1e-3) / HBM_PEAK)
+        out[name] = st
+    out["decoder_hbm_fraction_recorded"] = DECODER_HBM_FRACTION
+    del z_src, z_dst, pos
+    torch.cuda.empty_cache()
+    return out
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--configs", default="cfg2,cfg3")
+    ap.add_argument("--k", default="1,4")
+    ap.add_argument("--scale", type=float, default=1.0, help="multiply every node / edge count (tiny runs)")
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--target-ms", type=float, default=30.0, help="device time of one timed repeat, at least")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args(argv)
+    if args.repeats < 5:
+        ap.error("--repeats must be at least 5")
+    shapes = plan(args.configs.split(","), [int(v) for v in args.k.split(",")], args.scale)
+    for s in shapes:
+        print("plan:", json.dumps(s), file=sys.stderr)
+
+    import torch
+    if not torch.cuda.is_available():
+        print("bench_linkpred: no HIP device is visible; the link-prediction path has no CPU fallback", file=sys.stderr)
+        return 2
+    from hgin import _lib
+    _lib.lib()
+    results = [run_shape(torch, s, args.repeats, args.warmup, args.target_ms) for s in shapes]
+    both = [r for r in results if "error" not in r["link_loss"]]
+    doc = {"tool": "tools/bench_linkpred.py", "device": torch.cuda.get_device_name(0), "hbm_peak_bytes_per_s": HBM_PEAK,
+           "repeats": args.repeats, "warmup": args.warmup, "shapes": results,
+           "fused_faster_at_every_shape_both_ran": all(r["fused_faster_beyond_spread"] for r in both)}
+    text = json.dumps(doc)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(doc, indent=1) + "\n")
+    print(text)
+    return 0 if doc["fused_faster_at_every_shape_both_ran"] else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
