@@ -176,6 +176,9 @@ _SIGS = {
     "hgin_link_loss_bwd_src_f32": ([_P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _P, _I64, _P], _I32),
     "hgin_link_loss_bwd_dst_f32": ([_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _I64, _I64, _P, _I64, _P], _I32),
     "hgin_link_rank_f32": ([_P, _I64, _I64, _U64, _U64, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _P], _I32),
+    "hgin_link_full_rank_workspace_size": ([_I64, _I64, _I64, ctypes.POINTER(_SZ)], _I32),
+    "hgin_link_full_rank_f32": ([_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _P, _P, _P, _P, _SZ, _P],
+                                _I32),
     "hgin_aggregate_long_f32": ([_P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I32, _P, _I64, _P,
                                  _SZ, _P], _I32),
     "hgin_aggregate_long_bf16": ([_P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I32, _P, _I64, _P,
@@ -206,7 +209,7 @@ _SIGS = {
     "hgin_trace_enable": ([_I32], _I32),
     "hgin_trace_read": ([ctypes.c_char_p, _SZ], _SZ),
 }
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 def lib() -> ctypes.CDLL:

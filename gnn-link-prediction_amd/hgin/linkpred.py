@@ -13,6 +13,10 @@ Training path (A13 / A14, also not in the reference): ``sampled_link_loss`` is `
 deterministic store-and-sum backward; ``link_ranks`` / ``link_metrics`` evaluate with the same kernel and another
 epilogue; ``LinkPredictor`` puts them behind ``model.encode`` (hgin/train.py::link_train_step).  ``link_loss`` and
 the unfused pieces stay as the baseline the fused path is checked and timed against (tools/bench_linkpred.py).
+
+Full evaluation (A15, not in the reference either): ``link_full_ranks`` / ``link_full_metrics`` /
+``LinkPredictor.full_metrics`` rank every positive against *every* destination, optionally filtered by a set of known
+edges, on the fp32 matrix cores without materialising a score (csrc/hgin_linkrank.hip).
 """
 from __future__ import annotations
 
@@ -236,6 +240,95 @@ def link_metrics(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, o
     return metrics_from_ranks(n_gt, n_eq, k)
 
 
+# ---------------------------------------------------------------------------------------------------
+# A15: full-candidate filtered ranking (NOT IN REFERENCE)
+# ---------------------------------------------------------------------------------------------------
+def _known_csr(known: Tensor, n_src: int, n_dst: int):
+    """(rowptr int32 [n_src + 1], col int32) of ``known`` by source: columns sorted within a row, duplicates removed.
+    Built (and range-checked, one host sync) once per tensor version and cached on the tensor."""
+    key = (int(n_src), int(n_dst))
+    cache = getattr(known, "_hgin_known_csr", None)
+    ver = known._version
+    if cache is not None and cache[0] == ver and key in cache[1]:
+        return cache[1][key]
+    ops.check_edge_index(known)
+    dev = known.device
+    if known.size(1):
+        lo, hi = known.amin(1), known.amax(1)
+        bounds = torch.stack([lo[0], hi[0], lo[1], hi[1]]).tolist()
+        if bounds[0] < 0 or bounds[1] >= n_src:
+            raise IndexError(f"known: src index out of range [0, {n_src})")
+        if bounds[2] < 0 or bounds[3] >= n_dst:
+            raise IndexError(f"known: dst index out of range [0, {n_dst})")
+    pairs = torch.unique(known[0] * int(n_dst) + known[1])   # sorted: by source, then by destination
+    if pairs.numel() >= 2**31:
+        raise ValueError("known: more than 2^31 distinct edges")
+    src = torch.div(pairs, int(n_dst), rounding_mode="floor")
+    col = (pairs - src * int(n_dst)).to(torch.int32)
+    rowptr = torch.zeros(n_src + 1, dtype=torch.int64, device=dev)
+    rowptr[1:] = torch.cumsum(torch.bincount(src, minlength=n_src), 0)
+    out = (rowptr.to(torch.int32), col if col.numel() else torch.zeros(1, dtype=torch.int32, device=dev))
+    if cache is None or cache[0] != ver:
+        cache = (ver, {})
+    cache[1][key] = out
+    try:
+        known._hgin_known_csr = cache
+    except (AttributeError, RuntimeError):
+        pass
+    return out
+
+
+def link_full_ranks(z_src: Tensor, z_dst: Tensor, pos: Tensor, known: Tensor = None):
+    """(n_greater, n_equal, n_cand), int32 [E] (include/hgin.h A15): every positive (s, d) of ``pos`` is ranked against
+    every destination c != d, minus the c with (s, c) in ``known`` (an edge index [2, M]; None: unfiltered).
+    n_greater / n_equal count the candidates scoring above / exactly equal to the positive, n_cand the candidates.
+    Scores are fp32 dot products on the matrix cores and are never written.  No gradient."""
+    what = "link_full_ranks"
+    ops.require_device(known, what=what)
+    z_src, z_dst, pos, _, E, _ = _link_operands(what, z_src, z_dst, pos, 1)
+    z_src, z_dst = z_src.detach(), z_dst.detach()
+    dev = z_src.device
+    n_src, n_dst, F = int(z_src.size(0)), int(z_dst.size(0)), int(z_src.size(1))
+    if F < 1:
+        raise ValueError(f"{what}: embeddings need at least one feature")
+    rowptr = col = None
+    if known is not None:
+        rowptr, col = _known_csr(known, n_src, n_dst)
+    n_gt = torch.empty(E, dtype=torch.int32, device=dev)
+    n_eq = torch.empty(E, dtype=torch.int32, device=dev)
+    n_cand = torch.empty(E, dtype=torch.int32, device=dev)
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(_lib.lib().hgin_link_full_rank_workspace_size(E, n_dst, F, ctypes.byref(nbytes)),
+               "hgin_link_full_rank_workspace_size")
+    ws = ops._workspace(nbytes.value, dev)
+    _lib.call("hgin_link_full_rank_f32", ops._p(pos), E, n_src, n_dst, ops._p(z_src), z_src.stride(0), ops._p(z_dst),
+              z_dst.stride(0), F, ops._p(rowptr), ops._p(col), ops._p(n_gt), ops._p(n_eq), ops._p(n_cand), ops._p(ws),
+              nbytes.value, ops._stream(n_gt))
+    return n_gt, n_eq, n_cand
+
+
+def full_metrics_from_ranks(n_greater: Tensor, n_equal: Tensor, n_cand: Tensor) -> dict:
+    """Full ranking metrics as 0-dim float64 tensors on the counts' device (nothing is synchronised), keys as
+    ``metrics_from_ranks``: rank = 1 + greater + equal / 2 (ties share the middle rank), mrr = mean 1 / rank,
+    hits@K = mean [rank <= K], auc = mean over the queries that have a candidate of
+    1 - (greater + equal / 2) / n_cand."""
+    gt, eq, nc = n_greater.to(torch.float64), n_equal.to(torch.float64), n_cand.to(torch.float64)
+    above = gt + 0.5 * eq
+    rank = 1.0 + above
+    has = nc > 0
+    per_query = torch.where(has, 1.0 - above / torch.where(has, nc, torch.ones_like(nc)), torch.zeros_like(nc))
+    out = {"auc": per_query.sum() / has.to(torch.float64).sum(), "mrr": (1.0 / rank).mean()}
+    for K in (1, 3, 10):
+        out[f"hits@{K}"] = (rank <= K).to(torch.float64).mean()
+    return out
+
+
+def link_full_metrics(z_src: Tensor, z_dst: Tensor, pos: Tensor, known: Tensor = None) -> dict:
+    """auc / mrr / hits@1 / hits@3 / hits@10 of the positives against every (filtered) destination, as float64
+    device scalars: ``link_full_ranks`` + a few reductions over [E]; no host sync before the caller reads a value."""
+    return full_metrics_from_ranks(*link_full_ranks(z_src, z_dst, pos, known))
+
+
 class LinkPredictor:
     """Link-prediction head over a model's node embeddings: ``relation`` = (src_type, name, dst_type), k uniform
     negatives per positive, dot-product decoder, BCE-with-logits (``sampled_link_loss``)."""
@@ -265,5 +358,21 @@ class LinkPredictor:
             with torch.no_grad():
                 z = self.model.encode(graph.x_dict(), graph.edge_index_dict())
                 return link_metrics(z[self.relation[0]], z[self.relation[2]], pos, self.k, self.seed)
+        finally:
+            self.model.train(was_training)
+
+    def full_metrics(self, graph, pos: Tensor = None, known: Tensor = None) -> dict:
+        """``link_full_metrics`` of the model's embeddings in eval mode, without gradients (the mode is restored):
+        ``pos`` (default: the relation's own edges) ranked against every destination, filtered by ``known`` (default:
+        the relation's own edges in ``graph``; for held-out positives pass train + valid + test edges)."""
+        pos = self._pos(graph, pos)
+        if known is None:
+            known = graph.edge_index[self.relation]
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                z = self.model.encode(graph.x_dict(), graph.edge_index_dict())
+                return link_full_metrics(z[self.relation[0]], z[self.relation[2]], pos, known)
         finally:
             self.model.train(was_training)

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HGIN_ABI_VERSION 9
+#define HGIN_ABI_VERSION 10
 
 #define HGIN_OK 0
 #define HGIN_E_ARG (-1)        /* bad size / null pointer / unsupported combination */
@@ -461,6 +461,29 @@ int hgin_link_loss_bwd_dst_f32(const int32_t* pos_rowptr, const int32_t* pos_col
 int hgin_link_rank_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64_t seed, uint64_t offset, int64_t n_dst,
                        const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F,
                        int32_t* n_greater, int32_t* n_equal, void* stream);
+
+/* ---- A15: full-candidate filtered ranking (NOT IN REFERENCE; build-defined, ABI 10) ----------------------------
+ * For query q (s = pos[0, q], d = pos[1, q]; pos int64 [2, E] as in A13) and score(q, c) = <z_src[s], z_dst[c]>, the
+ * candidate set C(q) is every c in [0, n_dst) with c != d and, when known_rowptr is given, (s, c) not a known edge.
+ *   n_greater[q] = |{c in C(q): score(q, c) >  score(q, d)}|
+ *   n_equal[q]   = |{c in C(q): score(q, c) == score(q, d)}|
+ *   n_cand[q]    = |C(q)| = n_dst - 1 - |distinct known neighbours of s other than d|        (all int32 [E])
+ * known_rowptr int32 [n_src + 1] / known_col int32: a CSR by source whose columns are sorted within each row;
+ * repeated columns count once, columns outside [0, n_dst) are ignored.  known_rowptr = NULL: unfiltered.
+ * Scores are exact-fp32 matrix-core dot products (v_mfma_f32_32x32x2_f32), features taken in blocks of 8 in ascending
+ * order, inside a block in the pairs (0, 4), (1, 5), (2, 6), (3, 7); threshold, sweep and filter use this one
+ * sequence, so a destination row equal to row d is counted in n_equal wherever it lies.  No score is written: every
+ * 128-query block streams z_dst once and keeps two counters per query in registers; counts are joined by integer
+ * atomics and the known neighbours' contributions are subtracted afterwards (deterministic, run-to-run identical).
+ * Workspace: hgin_link_full_rank_workspace_size (one float per query).  fp32 only; rows need no alignment (16-byte
+ * loads are used when F, both strides and both bases allow them).  1 <= E < 2^31, 1 <= n_src, n_dst < 2^31,
+ * 1 <= F < 2^24, ld >= F: HGIN_E_ARG before any launch otherwise, also for known_rowptr without known_col;
+ * HGIN_E_WORKSPACE for a workspace that is NULL or too small.  E * n_dst may exceed 2^31. */
+int hgin_link_full_rank_workspace_size(int64_t n_pos, int64_t n_dst, int64_t F, size_t* bytes);
+int hgin_link_full_rank_f32(const int64_t* pos, int64_t n_pos, int64_t n_src, int64_t n_dst, const float* z_src,
+                            int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F,
+                            const int32_t* known_rowptr, const int32_t* known_col, int32_t* n_greater,
+                            int32_t* n_equal, int32_t* n_cand, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- F4 widening: HetroGAT's graph attention (models.py:380-506, PyG 2.0.2 GATConv) ---------------------------
  * x_s / x_d: projected source / destination features [N, H * C] (row stride ld*), edges = the relation after
