@@ -155,15 +155,9 @@ __device__ __forceinline__ float dot_piece(float acc, const float (&a)[VEC], con
   return acc;
 }
 
-template <int VEC>
-__device__ __forceinline__ void axpy_piece(float (&acc)[VEC], float w, const float (&x)[VEC]) {
-#pragma unroll
-  for (int c = 0; c < VEC; ++c) acc[c] = __fadd_rn(acc[c], __fmul_rn(w, x[c]));
-}
-
-// The same step with Kahan's compensation (same item order, still no FMA): the destination side uses it because a
-// destination's pair count E (1 + k) / n_dst has no bound (few destinations: thousands of terms that largely cancel),
-// where a plain fp32 running sum loses sqrt(n) eps of its largest partial sum.
+// acc += w * x with Kahan's compensation (item order kept, mul / add / sub only, no FMA).  Both gradient kernels use
+// it because a row's item count has no bound (few destinations, or a hub source owning thousands of positives:
+// thousands of terms that largely cancel), where a plain fp32 running sum loses sqrt(n) eps of its largest partial sum.
 template <int VEC>
 __device__ __forceinline__ void axpy_comp_piece(float (&acc)[VEC], float (&comp)[VEC], float w, const float (&x)[VEC]) {
 #pragma unroll
@@ -344,7 +338,8 @@ __global__ __launch_bounds__(256) void k_link_loss_sum(const float* __restrict__
 
 // Source-side gradient: a group per source row over the static CSC of the positives (rowptr / col = dst / perm =
 // edge id).  Items of the row in order: for each of its positives in CSC order, t = 0 (the positive's destination)
-// then its k negatives; acc += (g * c) * z_dst[id], kInFlight rows loaded per batch, added in item order.
+// then its k negatives; acc += (g * c) * z_dst[id], kInFlight rows loaded per batch, added in item order,
+// compensated (Kahan) like the destination side: a hub source's deg (k + 1) items are as unbounded as a destination's.
 template <int VEC, int G>
 __global__ __launch_bounds__(256) void k_link_bwd_src(const int32_t* __restrict__ rowptr,
                                                       const int32_t* __restrict__ col,
@@ -363,9 +358,9 @@ __global__ __launch_bounds__(256) void k_link_bwd_src(const int32_t* __restrict_
   const int beg = rowptr[r], end = rowptr[r + 1];
   const int64_t n_items = (int64_t)(end - beg) * (k + 1);
   for (int f = gl * VEC; f < F; f += G * VEC) {
-    float acc[VEC];
+    float acc[VEC], comp[VEC];
 #pragma unroll
-    for (int c = 0; c < VEC; ++c) acc[c] = 0.0f;
+    for (int c = 0; c < VEC; ++c) acc[c] = comp[c] = 0.0f;
     int p = beg, t = 0;
     // ids and weights of items i .. i + 3, branch-free so that each level of the index chain (perm / col, then the
     // drawn id and the coefficient) is one batch of independent loads; items past the end repeat the last one
@@ -406,7 +401,7 @@ __global__ __launch_bounds__(256) void k_link_bwd_src(const int32_t* __restrict_
       for (int u = 0; u < kInFlight; ++u) ld_piece<VEC>(zd + id[u] * ldd + f, x[u]);
 #pragma unroll
       for (int u = 0; u < kInFlight; ++u)
-        if (i + u < n_items) axpy_piece<VEC>(acc, w[u], x[u]);
+        if (i + u < n_items) axpy_comp_piece<VEC>(acc, comp, w[u], x[u]);
     }
     st_piece<VEC>(gz + r * ldg + f, acc);
   }

@@ -33,6 +33,14 @@ def ref_full_ranks(zs, zd, pos, known):
     return ((score > thr) & mask).sum(1), ((score == thr) & mask).sum(1), mask.sum(1)
 
 
+def ref_full_ranks_chunked(zs, zd, pos, known, rows=2048):
+    """``ref_full_ranks`` evaluated ``rows`` queries at a time and concatenated: the same counts (a query's counts
+    depend on no other query) without the [E, n_dst] float64 score matrix of a large E."""
+    pos = np.asarray(pos)
+    parts = [ref_full_ranks(zs, zd, pos[:, i:i + rows], known) for i in range(0, pos.shape[1], rows)]
+    return tuple(np.concatenate([p[j] for p in parts]) for j in range(3))
+
+
 def ref_full_bands(zs, zd, pos, known):
     """Bounds that hold for every fp32 (or split) accumulation order: with b[q, c] = 2 F 2^-24 sum_f |zs[s, f]
     zd[c, f]|, returns (gt_lo, gt_hi, ge_lo, ge_hi, n_cand): n_greater lies in [gt_lo, gt_hi] = [#score > thr + b,
@@ -84,6 +92,30 @@ def test_reference_on_the_hand_computed_case():
     m = ref_full_metrics(gt, eq, nc)   # ranks 1.5, 1, 2.5, 1; auc over q0 and q2 only: 0.75 and 0.25
     assert abs(m["mrr"] - (2 / 3 + 1 + 0.4 + 1) / 4) < 1e-15 and m["auc"] == 0.5
     assert m["hits@1"] == 0.5 and m["hits@3"] == 1.0 and m["hits@10"] == 1.0
+
+
+def test_chunked_reference_equals_the_reference():
+    """Chunks that do and do not divide E, a chunk of one query, one chunk for everything; with and without the
+    filter (repeated known edges, a source connected to everything), on integers so that ties occur."""
+    g = np.random.default_rng(17)
+    E, n_src, n_dst, F = 203, 9, 37, 5
+    zs = g.integers(-2, 3, (n_src, F)).astype(np.float32)
+    zd = g.integers(-2, 3, (n_dst, F)).astype(np.float32)
+    pos = np.stack([g.integers(0, n_src, E), g.integers(0, n_dst, E)])
+    known = np.concatenate([pos[:, :120], pos[:, :40], np.stack([np.full(n_dst, 4), np.arange(n_dst)]),
+                            np.stack([g.integers(0, n_src, 60), g.integers(0, n_dst, 60)])], 1)
+    for kn in (None, known):
+        want = ref_full_ranks(zs, zd, pos, kn)
+        assert int(want[1].sum()) > 0 and int(want[0].sum()) > 0
+        if kn is not None:
+            assert int((want[2] == 0).sum()) > 0 and int(want[2].max()) < n_dst - 1
+        for rows in (1, 7, 50, 203, 1000):
+            got = ref_full_ranks_chunked(zs, zd, pos, kn, rows=rows)
+            assert len(got) == 3
+            for a, b in zip(got, want):
+                assert a.shape == (E,) and a.dtype == b.dtype and np.array_equal(a, b), rows
+    got = ref_full_ranks_chunked(ZS, ZD, POS, KNOWN, rows=3)
+    assert [v.tolist() for v in got] == [[0, 0, 1, 0], [1, 0, 1, 0], [2, 0, 2, 0]]
 
 
 def test_full_metrics_from_ranks_on_cpu_counts():
