@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <string>
 
 #include "../../include/hgin.h"
@@ -128,6 +129,57 @@ __device__ __forceinline__ void split4(const float4 v, uint2 (&o)[3]) {
 // 16 rows of a ds_read_b128 lane group fall on 16 distinct 16-B bank slots (13 is odd).
 constexpr int kSplitRowWords = 52;
 bool gemm_split_enabled();   // HGIN_F32_GEMM=mfma32 selects the exact f32-MFMA kernels; default split
+
+// Operand fragment and accumulator tile of v_mfma_f32_32x32x16_bf16.
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+
+// The six products of one split-mode k-step, planes indexed 0 = a1 (the leading bf16) .. 2 = a3: smallest terms
+// first (a3b1, a2b2, a1b3, a2b1, a1b2, a1b1), so the small terms are not absorbed by an already large accumulator.
+// Every split-mode kernel forms its products here: the bitwise switch tests between the tiled and the
+// weight-stationary kernels (tests/test_gpu_gemm_switch.py, tests/test_gpu_wsd_tail.py) rest on this one order.
+__device__ __forceinline__ void split_mfma6(f32x16& acc, const bf16x8 (&a)[3], const bf16x8 (&b)[3]) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
+}
+// (fragments held as the uint4 of their ds_read_b128)
+__device__ __forceinline__ void split_mfma6(f32x16& acc, const uint4 (&a)[3], const uint4 (&b)[3]) {
+  const bf16x8 fa[3] = {__builtin_bit_cast(bf16x8, a[0]), __builtin_bit_cast(bf16x8, a[1]),
+                        __builtin_bit_cast(bf16x8, a[2])};
+  const bf16x8 fb[3] = {__builtin_bit_cast(bf16x8, b[0]), __builtin_bit_cast(bf16x8, b[1]),
+                        __builtin_bit_cast(bf16x8, b[2])};
+  split_mfma6(acc, fa, fb);
+}
+
+template <int A, int B>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[A][B]) {
+#pragma unroll
+  for (int a = 0; a < A; ++a)
+#pragma unroll
+    for (int b = 0; b < B; ++b)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.0f;
+}
+
+// A value the compiler cannot see through (the thread index, re-read where used inside a loop): the per-lane DMA /
+// split offsets derived from it are recomputed per block instead of being hoisted out of the loop into registers
+// (which spills the K = 512 weight-stationary kernels, whose W slice alone holds 128 VGPRs).
+__device__ __forceinline__ int opaque(int v) {
+  int t;
+  asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(v));
+  return t;
+}
+
+// An on / off environment switch: on by default, off when the value starts with '0'.  Callers keep the result in a
+// function-local static, so each switch is read once.
+inline bool env_switch_on(const char* name) {
+  const char* v = getenv(name);
+  return !(v && v[0] == '0');
+}
 
 // LDS-DMA (global_load_lds_dwordx4: 64 lanes x 16 B into 1 KiB at a wave-uniform LDS address) issued from
 // inline asm: the compiler does not see it, so it does not guard the kernel's later LDS reads with a vmcnt(0)

@@ -617,11 +617,8 @@ __global__ __launch_bounds__(256) void k_gat_bwd_src_w(const int32_t* __restrict
 
 // The wave-group form applies: C a multiple of 4 with C / 4 a power of two, H * C <= 256, 16-B aligned rows.
 int gat_group(int64_t H, int64_t C) {
-  static const bool off = [] {
-    const char* v = getenv("HGIN_GAT_WAVE");
-    return v && v[0] == '0';
-  }();
-  if (off || C % 4 || ((C / 4) & (C / 4 - 1)) || H * C > 256) return 0;
+  static const bool on = env_switch_on("HGIN_GAT_WAVE");
+  if (!on || C % 4 || ((C / 4) & (C / 4 - 1)) || H * C > 256) return 0;
   int g = 1;
   while (g < H * C / 4) g <<= 1;
   return g < (int)H ? 0 : g;

@@ -33,8 +33,6 @@
 namespace hgin {
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
 constexpr int kBK = 32;
 constexpr int kLds = kBK + 4;
 
@@ -372,8 +370,6 @@ __device__ __forceinline__ void epilogue(const AccT& acc, float* smem, int wave,
   if (EPI == 4) *ep_out = ep;
 }
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-
 // EPI 4: the workgroup's eps-gradient partial, a fixed tree over its 256 lanes -> part[tile]
 __device__ __forceinline__ void tile_partial(float* smem, float ep, float* part, int64_t q) {
   __syncthreads();   // the epilogue's LDS staging is done
@@ -429,7 +425,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || TN == 4) ? 2 : 3) void k_gemm_
 
   f32x16 acc[2][TN];
 #pragma unroll
-  for (int a = 0; a < 2; ++a)
+  for (int a = 0; a < 2; ++a)   // (written out: through zero_acc the tiled kernels' scalar code schedules differently)
 #pragma unroll
     for (int b = 0; b < TN; ++b)
 #pragma unroll
@@ -507,14 +503,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || TN == 4) ? 2 : 3) void k_gemm_
             fb[p] = *reinterpret_cast<const bf16x8*>(Bcur + (wn * WCOLS + tn * 32 + li) * kSplitRowWordsNT + p * 16 +
                                                      nt_chunk(li, kb * 2 + lh));
 #pragma unroll
-          for (int tm = 0; tm < 2; ++tm) {   // smallest terms first
-            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][2], fb[0], acc[tm][tn], 0, 0, 0);
-            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][1], fb[1], acc[tm][tn], 0, 0, 0);
-            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][0], fb[2], acc[tm][tn], 0, 0, 0);
-            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][1], fb[0], acc[tm][tn], 0, 0, 0);
-            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][0], fb[1], acc[tm][tn], 0, 0, 0);
-            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][0], fb[0], acc[tm][tn], 0, 0, 0);
-          }
+          for (int tm = 0; tm < 2; ++tm) split_mfma6(acc[tm][tn], fa[tm], fb);
         }
       }
     } else {
@@ -556,10 +545,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || TN == 4) ? 2 : 3) void k_gemm_
 
 // HGIN_NT_BDMA=0: the 128 x 128 split-mode tile splits B itself even where pre-split planes are passed
 bool nt_bdma_enabled() {
-  static const bool on = [] {
-    const char* v = getenv("HGIN_NT_BDMA");
-    return !(v && v[0] == '0');
-  }();
+  static const bool on = env_switch_on("HGIN_NT_BDMA");
   return on;
 }
 
@@ -808,7 +794,7 @@ __global__ __launch_bounds__(256, BKH <= 64 ? 3 : 2) void k_gemm_nt_bf16(Src2h A
 
   f32x16 acc[2][TN];
 #pragma unroll
-  for (int a = 0; a < 2; ++a)
+  for (int a = 0; a < 2; ++a)   // (written out: through zero_acc the tiled kernels' scalar code schedules differently)
 #pragma unroll
     for (int b = 0; b < TN; ++b)
 #pragma unroll
@@ -1065,17 +1051,9 @@ __global__ __launch_bounds__((WsCfg<K, N, CPW>::NT), (ws_wpc<K, N, CPW>())) void
   // addresses: a block-uniform 64-bit base (row r0) plus a 32-bit per-lane offset (rows past M clamp to M - 1:
   // their products land in rows that are never stored)
   const int ki = (int)k1;
-  // the thread index as an opaque value, re-read where used inside the loop: the per-lane DMA / scaling offsets
-  // derived from it are then recomputed per block instead of being hoisted out of the loop into registers
-  // (which spills the K = 512 kernels, whose W slice alone holds 128 VGPRs)
-  auto tid_o = [&]() {
-    int t;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(tid));
-    return t;
-  };
   auto issue_rows = [&](const uint16_t* p, int64_t ld, char* img, int64_t r0, int rmax) {
     const uint16_t* pb = p + r0 * ld;
-    const int lane = tid_o() & 63;
+    const int lane = opaque(tid) & 63;
 #pragma unroll
     for (int q = 0; q < C::PC; ++q) {
       const int piece = wave * C::PC + q;
@@ -1090,7 +1068,7 @@ __global__ __launch_bounds__((WsCfg<K, N, CPW>::NT), (ws_wpc<K, N, CPW>())) void
     const int rmax = (int)(M - 1 - r0 < C::BM ? M - 1 - r0 : C::BM - 1);
     const uint16_t* b1 = g.a1 + r0 * g.lda1;
     const uint16_t* b2 = g.a2 + r0 * g.lda2;
-    const int lane = tid_o() & 63;
+    const int lane = opaque(tid) & 63;
 #pragma unroll
     for (int q = 0; q < C::PA; ++q) {
       const int piece = wave * C::PA + q;
@@ -1131,7 +1109,7 @@ __global__ __launch_bounds__((WsCfg<K, N, CPW>::NT), (ws_wpc<K, N, CPW>())) void
     if (scale_any) {
       constexpr int CH = C::A_BYTES / 16;                        // 16-B chunks of the A image
       constexpr int RC = C::ROWB / 16;                           // chunks per image row
-      const int tq = tid_o();
+      const int tq = opaque(tid);
       constexpr bool kHalf = K >= 256 && (CH / 2) % C::NT == 0;
       if (kHalf && k1 == K / 2) {
         // equal halves (the concat of a 256-wide aggregate and a 256-wide x_dst): the row swizzle c ^ (r & 15) keeps
@@ -1166,12 +1144,7 @@ __global__ __launch_bounds__((WsCfg<K, N, CPW>::NT), (ws_wpc<K, N, CPW>())) void
     uint16_t* zb = kZ ? g.z + r0 * ldz : nullptr;
 
     f32x16 acc[C::TM][C::TN];
-#pragma unroll
-    for (int tm = 0; tm < C::TM; ++tm)
-#pragma unroll
-      for (int tn = 0; tn < C::TN; ++tn)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[tm][tn][e] = 0.0f;
+    zero_acc(acc);
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int t = 0; t < C::KS; ++t) {
@@ -1263,10 +1236,7 @@ __global__ __launch_bounds__((WsCfg<K, N, CPW>::NT), (ws_wpc<K, N, CPW>())) void
 // K 128 / 256 / 512, k1 a multiple of 8, 16-B aligned rows everywhere (leading dimensions multiples of 8), W
 // packed [N, K]; EPI 1 (forward MLP), EPI 0 (plain dX) and EPI 4 with the self term on every column (cs = 0).
 bool ws_enabled() {
-  static const bool on = [] {
-    const char* v = getenv("HGIN_NT_WS");
-    return !(v && v[0] == '0');
-  }();
+  static const bool on = env_switch_on("HGIN_NT_WS");
   return on;
 }
 
@@ -1481,11 +1451,6 @@ __global__ __launch_bounds__((Ws32Cfg<K, N>::NT), 1) void k_ws_f32(WsArgs32 g) {
   auto dma = [&](const void* src, void* dst) {
     if (g.nt_in) glds16_asm<true>(src, dst); else glds16_asm(src, dst);
   };
-  auto tid_o = [&]() {
-    int t;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(tid));
-    return t;
-  };
   auto rows_of = [&](int64_t i, int64_t& r0, int& rmax) {
     r0 = ((int64_t)blockIdx.x + i * G) * C::BM;
     rmax = (int)(M - 1 - r0 < C::BM ? M - 1 - r0 : C::BM - 1);
@@ -1496,7 +1461,7 @@ __global__ __launch_bounds__((Ws32Cfg<K, N>::NT), 1) void k_ws_f32(WsArgs32 g) {
     int rmax;
     rows_of(i, r0, rmax);
     const float* ab = g.a + r0 * g.lda;
-    const int ln = tid_o() & 63;
+    const int ln = opaque(tid) & 63;
 #pragma unroll
     for (int q = 0; q < C::PA; ++q) {
       const int piece = wave * C::PA + q;
@@ -1511,7 +1476,7 @@ __global__ __launch_bounds__((Ws32Cfg<K, N>::NT), 1) void k_ws_f32(WsArgs32 g) {
     int rmax;
     rows_of(i, r0, rmax);
     const float* cb = src + r0 * ld;
-    const int ln = tid_o() & 63;
+    const int ln = opaque(tid) & 63;
 #pragma unroll
     for (int q = 0; q < C::PC; ++q) {
       const int piece = wave * C::PC + q;
@@ -1534,7 +1499,7 @@ __global__ __launch_bounds__((Ws32Cfg<K, N>::NT), 1) void k_ws_f32(WsArgs32 g) {
     if (i + 1 < my) issue_a(i + 1);
     const char* abase = ws32_smem + (int)(i % R::NST) * C::A_BYTES;
     {   // split pass: the fp32 image -> the three plane images
-      const int t = tid_o();
+      const int t = opaque(tid);
 #pragma unroll
       for (int j = 0; j < C::G4; ++j) {
         const int grp = j * C::NT + t;
@@ -1559,7 +1524,7 @@ __global__ __launch_bounds__((Ws32Cfg<K, N>::NT), 1) void k_ws_f32(WsArgs32 g) {
     for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
     // A fragments double-buffered one k-step ahead; the scheduling fences keep the compiler from hoisting every
     // k-step's fragment reads to the top of the block (3 x 4 x KS VGPRs on top of the W slice)
-    const int fl = tid_o() & 63;
+    const int fl = opaque(tid) & 63;
     const int frow = (fl & 31) * C::PROW;
     const int fsw = ((fl >> 5) ^ (fl & 31)) & C::SW;          // (2t + lh) ^ (li & SW) = 2t ^ fsw for 2t even
     auto frag = [&](int t, uint4 (&f)[3]) {
@@ -1574,17 +1539,7 @@ __global__ __launch_bounds__((Ws32Cfg<K, N>::NT), 1) void k_ws_f32(WsArgs32 g) {
 #pragma unroll
     for (int t = 0; t < C::KS; ++t) {
       if (t + 1 < C::KS) frag(t + 1, fa[(t + 1) & 1]);
-      const uint4(&f)[3] = fa[t & 1];
-      const bf16x8 a0 = __builtin_bit_cast(bf16x8, f[0]), a1 = __builtin_bit_cast(bf16x8, f[1]),
-                   a2 = __builtin_bit_cast(bf16x8, f[2]);
-      const bf16x8 b0 = __builtin_bit_cast(bf16x8, wf[t][0]), b1 = __builtin_bit_cast(bf16x8, wf[t][1]),
-                   b2 = __builtin_bit_cast(bf16x8, wf[t][2]);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b0, acc, 0, 0, 0);   // k_gemm_nt's order
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b2, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc, 0, 0, 0);
+      split_mfma6(acc, fa[t & 1], wf[t]);
       __builtin_amdgcn_sched_barrier(0);
     }
     __builtin_amdgcn_s_setprio(0);
@@ -1615,7 +1570,7 @@ __global__ __launch_bounds__((Ws32Cfg<K, N>::NT), 1) void k_ws_f32(WsArgs32 g) {
     asm volatile("" ::: "memory");
 #pragma unroll
     for (int pass = 0; pass < 4; ++pass) {
-      const int tq = tid_o();
+      const int tq = opaque(tid);
       const int cq = (tq % QPR) * 4;
       const int brow = pass * 8 + tq / QPR;
       const int64_t grow = r0 + brow;
@@ -1668,10 +1623,7 @@ __global__ __launch_bounds__((Ws32Cfg<K, N>::NT), 1) void k_ws_f32(WsArgs32 g) {
 
 // HGIN_NT_WS32 = 0 keeps the tiled kernel for the fp32 forward GEMM.
 bool ws32_enabled() {
-  static const bool on = [] {
-    const char* v = getenv("HGIN_NT_WS32");
-    return !(v && v[0] == '0');
-  }();
+  static const bool on = env_switch_on("HGIN_NT_WS32");
   return on;
 }
 
@@ -1775,11 +1727,6 @@ __global__ __launch_bounds__(512, 1) void k_wss_f32(WsArgs32 g) {
 #pragma unroll
     for (int p = 0; p < 3; ++p) asm volatile("" ::"v"(wf[t][p].x), "v"(wf[t][p].y), "v"(wf[t][p].z), "v"(wf[t][p].w));
 
-  auto tid_o = [&]() {
-    int t;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(tid));
-    return t;
-  };
   auto dma = [&](const void* src, void* dst) {
     if (g.nt_in) glds16_asm<true>(src, dst); else glds16_asm(src, dst);
   };
@@ -1787,7 +1734,7 @@ __global__ __launch_bounds__(512, 1) void k_wss_f32(WsArgs32 g) {
     const int64_t r0 = ((int64_t)blockIdx.x + i * G) * C::BM;
     const int rmax = (int)(M - 1 - r0 < C::BM ? M - 1 - r0 : C::BM - 1);
     const float* ab = g.a + r0 * g.lda;
-    const int ln = tid_o() & 63;
+    const int ln = opaque(tid) & 63;
 #pragma unroll
     for (int q = 0; q < C::PA; ++q) {
       const int piece = wave * C::PA + q;
@@ -1802,7 +1749,7 @@ __global__ __launch_bounds__(512, 1) void k_wss_f32(WsArgs32 g) {
     const int64_t r0 = ((int64_t)blockIdx.x + i * G) * C::BM;
     const int rmax = (int)(M - 1 - r0 < C::BM ? M - 1 - r0 : C::BM - 1);
     const float* src = g.r1 + r0 * g.ldr1 + wave * 32;
-    const int ln = tid_o() & 63;
+    const int ln = opaque(tid) & 63;
 #pragma unroll
     for (int q = 0; q < PR; ++q) {
       int r = q * 8 + (ln >> 3);
@@ -1813,7 +1760,7 @@ __global__ __launch_bounds__(512, 1) void k_wss_f32(WsArgs32 g) {
   // block j (in this wave's slice, landed) -> plane buffer j & 1; the slice is then refilled with block j + 1
   auto split = [&](int64_t j) {
     char* pl = wss_smem + PL0 + (int)(j & 1) * PLANES;
-    const int ln = tid_o() & 63;
+    const int ln = opaque(tid) & 63;
     float4 v[C::G4];
 #pragma unroll
     for (int q = 0; q < C::G4; ++q) v[q] = *reinterpret_cast<const float4*>(wss_smem + (wave * C::PA + q) * 1024 + ln * 16);
@@ -1840,7 +1787,7 @@ __global__ __launch_bounds__(512, 1) void k_wss_f32(WsArgs32 g) {
   auto mfma = [&](int64_t i) {   // k_ws_f32's fragments and product order
     const char* planes = wss_smem + PL0 + (int)(i & 1) * PLANES;
     if constexpr (kInit) {   // the partial of the first K half, this wave's 32 columns in the accumulator layout
-      const int il = tid_o() & 63;
+      const int il = opaque(tid) & 63;
       const float* img = reinterpret_cast<const float*>(rimg) + 4 * (il >> 5) * 32 + (il & 31);
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[e] = img[((e & 3) + 8 * (e >> 2)) * 32];
@@ -1848,7 +1795,7 @@ __global__ __launch_bounds__(512, 1) void k_wss_f32(WsArgs32 g) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
     }
-    const int fl = tid_o() & 63;
+    const int fl = opaque(tid) & 63;
     const int frow = (fl & 31) * C::PROW;
     const int fsw = ((fl >> 5) ^ (fl & 31)) & C::SW;
     auto frag = [&](int t, uint4 (&f)[3]) {
@@ -1862,17 +1809,7 @@ __global__ __launch_bounds__(512, 1) void k_wss_f32(WsArgs32 g) {
 #pragma unroll
     for (int t = 0; t < C::KS; ++t) {
       if (t + 1 < C::KS) frag(t + 1, fa[(t + 1) & 1]);
-      const uint4(&f)[3] = fa[t & 1];
-      const bf16x8 a0 = __builtin_bit_cast(bf16x8, f[0]), a1 = __builtin_bit_cast(bf16x8, f[1]),
-                   a2 = __builtin_bit_cast(bf16x8, f[2]);
-      const bf16x8 b0 = __builtin_bit_cast(bf16x8, wf[t][0]), b1 = __builtin_bit_cast(bf16x8, wf[t][1]),
-                   b2 = __builtin_bit_cast(bf16x8, wf[t][2]);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b0, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b2, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc, 0, 0, 0);
+      split_mfma6(acc, fa[t & 1], wf[t]);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -1886,7 +1823,7 @@ __global__ __launch_bounds__(512, 1) void k_wss_f32(WsArgs32 g) {
     const auto ry = __builtin_amdgcn_make_buffer_rsrc(g.y + r0 * ldy, 0, C::BM * ldy * 4, kRsrc);
     const auto rz = __builtin_amdgcn_make_buffer_rsrc(kZ ? g.z + r0 * ldz : g.y, 0, C::BM * ldz * 4, kRsrc);
     // lane offsets recomputed per block (tid_o hides tid's value): nothing of the epilogue stays live in VGPRs
-    const int el = tid_o() & 63, eli = el & 31, elh = el >> 5;
+    const int el = opaque(tid) & 63, eli = el & 31, elh = el >> 5;
     const int voy = (4 * elh * ldy + wave * 32 + eli) * 4, voz = (4 * elh * ldz + wave * 32 + eli) * 4;
     const float* img = reinterpret_cast<const float*>(rimg) + 4 * elh * 32 + eli;
 #pragma unroll

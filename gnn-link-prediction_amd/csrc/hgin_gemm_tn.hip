@@ -13,8 +13,6 @@
 namespace hgin {
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
 // ---------------------------------------------------------------------------------------------------
 // Weight-gradient GEMM "TN":  out[N, K] = A^T [B1 | B2],  A [M, N], B1 [M, K1], B2 [M, K - K1].
 // The reduction runs over M (every node of a type: 1e5..1e7 rows) and the output is small (H x K), so
@@ -107,8 +105,6 @@ __device__ __forceinline__ void pro_partials(const TnPro& pro, float* red, int c
 // TNR = output-tile rows along N: 128 (2 x 2 waves of 64 x 64) or 32 for narrow gradients such as the
 // readout's Linear(128, 32) (4 waves of 32 x 32 along K: no MFMA work on rows that do not exist; wave 0
 // alone stages the 32-column A block).
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-
 // kSplit: fp32 operands on the bf16 matrix cores (hgin_common.h split4): the transposed column runs of 4 m
 // are written as three bf16 planes ([col][3 x 32 m + pad] rows of kSplitRowWords words) and a lane reads
 // 8 consecutive m of a plane (one 16-deep k-block) per ds_read_b128.
@@ -360,14 +356,7 @@ __device__ __forceinline__ void tn_partial_body(const float* __restrict__ A, int
 #pragma unroll
         for (int tm = 0; tm < BMN; ++tm)
 #pragma unroll
-          for (int tn = 0; tn < BMK; ++tn) {   // smallest terms first
-            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][2], fb[tn][0], acc[tm][tn], 0, 0, 0);
-            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][1], fb[tn][1], acc[tm][tn], 0, 0, 0);
-            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][0], fb[tn][2], acc[tm][tn], 0, 0, 0);
-            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][1], fb[tn][0], acc[tm][tn], 0, 0, 0);
-            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][0], fb[tn][1], acc[tm][tn], 0, 0, 0);
-            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][0], fb[tn][0], acc[tm][tn], 0, 0, 0);
-          }
+          for (int tn = 0; tn < BMK; ++tn) split_mfma6(acc[tm][tn], fa[tm], fb[tn]);
       }
     } else {
   #pragma unroll
@@ -797,11 +786,6 @@ __global__ __launch_bounds__(512, 1) void k_wsd_bf16(const uint16_t* __restrict_
   if ((int64_t)blockIdx.x >= nblk) return;
   const int64_t my = (nblk - 1 - blockIdx.x) / G + 1;
 
-  auto tid_o = [&]() {   // opaque: keeps the per-lane DMA offsets from being hoisted into registers
-    int t;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(tid));
-    return t;
-  };
   auto dma = [&](const void* src, void* dst) { glds16_asm<true>(src, dst); };   // non-temporal: the rows stream
   const int k1 = (int)K1;
   const float sl = PRO ? pro.slope[0] : 0.0f;
@@ -811,7 +795,7 @@ __global__ __launch_bounds__(512, 1) void k_wsd_bf16(const uint16_t* __restrict_
     char* base = wsd_smem + (int)(i % NST) * C::SLOT;
     const int64_t r0 = ((int64_t)blockIdx.x + i * G) * C::BM;
     const int rmax = (int)(M - 1 - r0 < C::BM ? M - 1 - r0 : C::BM - 1);
-    const int ln = tid_o() & 63;
+    const int ln = opaque(tid) & 63;
     const uint16_t* ab = A + r0 * lda;
     const uint16_t* b1 = B1 + r0 * ldb1;
     const uint16_t* b2 = B2 + r0 * ldb2;
@@ -1054,11 +1038,6 @@ __global__ __launch_bounds__(512, 1) void k_wsd_f32(const float* __restrict__ A,
   const int64_t my = (nblk - 1 - blockIdx.x) / G + 1;
   char* const planes = wsdf_smem + C::SLOT * NST;
 
-  auto tid_o = [&]() {
-    int t;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(tid));
-    return t;
-  };
   auto dma = [&](const void* src, void* dst) { glds16_asm<true>(src, dst); };   // non-temporal: the rows stream
   const int k1 = (int)K1;
   // The clamped form: any block, rows past M included (start-up and a workgroup's last block only; see k_wsp_f32).
@@ -1066,7 +1045,7 @@ __global__ __launch_bounds__(512, 1) void k_wsd_f32(const float* __restrict__ A,
     char* base = wsdf_smem + (int)(i % NST) * C::SLOT;
     const int64_t r0 = ((int64_t)blockIdx.x + i * G) * C::BM;
     const int rmax = (int)(M - 1 - r0 < C::BM ? M - 1 - r0 : C::BM - 1);
-    const int ln = tid_o() & 63;
+    const int ln = opaque(tid) & 63;
     const float* ab = A + r0 * lda;
     const float* b1 = B1 + r0 * ldb1;
     const float* b2 = B2 + r0 * ldb2;
@@ -1203,7 +1182,7 @@ __global__ __launch_bounds__(512, 1) void k_wsd_f32(const float* __restrict__ A,
     const int valid = kTail ? (M - r0 < C::BM ? (int)(M - r0) : C::BM) : C::BM;
     {   // split both fp32 images into three bf16 planes, one float4 (half a 16-B plane chunk) per lane and step:
         // consecutive lanes read consecutive 16-B pieces (conflict-free; 32 B per lane was 2-way conflicted)
-      const int t = tid_o();
+      const int t = opaque(tid);
       constexpr int CA = C::CA, CT = C::BM * (N + K) / 4;   // float4 groups
       static_assert(CT % C::NT == 0 && CA % C::NT == 0, "every thread the same groups, A first");
 #pragma unroll
@@ -1285,14 +1264,7 @@ __global__ __launch_bounds__(512, 1) void k_wsd_f32(const float* __restrict__ A,
         fb[p] = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
       }
 #pragma unroll
-      for (int tm = 0; tm < 2; ++tm) {   // k_gemm_tn_partial's order: smallest terms first
-        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][2], fb[0], acc[tm][tn], 0, 0, 0);
-        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][1], fb[1], acc[tm][tn], 0, 0, 0);
-        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][0], fb[2], acc[tm][tn], 0, 0, 0);
-        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][1], fb[0], acc[tm][tn], 0, 0, 0);
-        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][0], fb[1], acc[tm][tn], 0, 0, 0);
-        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][0], fb[0], acc[tm][tn], 0, 0, 0);
-      }
+      for (int tm = 0; tm < 2; ++tm) split_mfma6(acc[tm][tn], fa[tm], fb);
     }
     __builtin_amdgcn_s_setprio(0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1400,11 +1372,6 @@ __global__ __launch_bounds__(512, 1) void k_wsp_f32(const float* __restrict__ A,
   const int64_t my = (nblk - 1 - blockIdx.x) / G + 1;
   char* const planes0 = wsp_smem + C::slot<PRO>();
 
-  auto tid_o = [&]() {
-    int t;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(tid));
-    return t;
-  };
   const int k1 = (int)K1;
   // Only a workgroup's last block can hold rows past M, so the row clamps, the zeroing of invalid rows and the dump
   // slot exist only in the kTail instantiations of issue / split (block 0's start-up and the last block); the
@@ -1429,7 +1396,7 @@ __global__ __launch_bounds__(512, 1) void k_wsp_f32(const float* __restrict__ A,
     if constexpr (decltype(tail)::value) {
       const int64_t r0 = ((int64_t)blockIdx.x + i * G) * C::BM;
       const int rmax = (int)(M - 1 - r0 < C::BM ? M - 1 - r0 : C::BM - 1);
-      const int ln = tid_o() & 63;
+      const int ln = opaque(tid) & 63;
       const float* ab = A + r0 * lda;
       const float* b1 = B1 + r0 * ldb1;
       const float* b2 = B2 + r0 * ldb2;
@@ -1503,7 +1470,7 @@ __global__ __launch_bounds__(512, 1) void k_wsp_f32(const float* __restrict__ A,
     char* pl = planes0 + (int)(j & 1) * C::PLANES;
     const int64_t r0 = kTail ? ((int64_t)blockIdx.x + j * G) * C::BM : 0;
     const int valid = kTail ? (M - r0 < C::BM ? (int)(M - r0) : C::BM) : C::BM;
-    const int ln = tid_o() & 63;
+    const int ln = opaque(tid) & 63;
     const int rw = 2 * wave;
     float4 va[2], vb[2], zv[2];
 #pragma unroll
@@ -1586,14 +1553,7 @@ __global__ __launch_bounds__(512, 1) void k_wsp_f32(const float* __restrict__ A,
         fb[p] = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
       }
 #pragma unroll
-      for (int tm = 0; tm < 2; ++tm) {
-        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][2], fb[0], acc[tm][tn], 0, 0, 0);
-        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][1], fb[1], acc[tm][tn], 0, 0, 0);
-        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][0], fb[2], acc[tm][tn], 0, 0, 0);
-        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][1], fb[0], acc[tm][tn], 0, 0, 0);
-        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][0], fb[1], acc[tm][tn], 0, 0, 0);
-        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tm][0], fb[0], acc[tm][tn], 0, 0, 0);
-      }
+      for (int tm = 0; tm < 2; ++tm) split_mfma6(acc[tm][tn], fa[tm], fb);
     }
   };
 
@@ -1664,19 +1624,13 @@ __global__ __launch_bounds__(512, 1) void k_wsp_f32(const float* __restrict__ A,
 // k1 a multiple of 8, 16-B aligned rows (leading dimensions multiples of 8, below 2^24).  Returns the slab
 // count, or 0 when it does not apply.
 bool wsd_enabled() {
-  static const bool on = [] {
-    const char* v = getenv("HGIN_TN_WS");
-    return !(v && v[0] == '0');
-  }();
+  static const bool on = env_switch_on("HGIN_TN_WS");
   return on;
 }
 
 // HGIN_WSD_PRO = 0 keeps the separate PReLU-backward pass (k_rows_bwd<0>) ahead of the weight-stationary dW.
 bool wsd_pro_enabled() {
-  static const bool on = [] {
-    const char* v = getenv("HGIN_WSD_PRO");
-    return !(v && v[0] == '0');
-  }();
+  static const bool on = env_switch_on("HGIN_WSD_PRO");
   return on;
 }
 
@@ -1690,58 +1644,65 @@ int64_t wsd_cus() {
   return g;
 }
 
-template <int NV, int KV, bool PRO = false>
-int64_t launch_wsd(const uint16_t* a, int64_t lda, const uint16_t* b1, int64_t ldb1, const uint16_t* b2,
-                   int64_t ldb2, int64_t k1, int64_t M, float* slab, int64_t ld_slab, int64_t grid, hipStream_t s,
-                   const WsdPro& pro = WsdPro{}) {
-  // (the streamed rows are DMA'd non-temporal: 1-3 % faster, profiles/r02/gemm_ws_bf16.txt)
-  constexpr int lds = WsdCfg<NV, KV, PRO>::SLOT * WsdCfg<NV, KV, PRO>::NST;
-  auto kern = k_wsd_bf16<NV, KV, PRO>;
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+// One kernel of the family: the dynamic-LDS attribute set once per instantiation, the launch traced.
+template <auto kKern, int kLds, typename T>
+int64_t wsd_launch(const char* name, int nv, int kv, bool fused, const T* a, int64_t lda, const T* b1, int64_t ldb1,
+                   const T* b2, int64_t ldb2, int64_t k1, int64_t M, float* slab, int64_t ld_slab, int64_t grid,
+                   hipStream_t s, const WsdPro& pro) {
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kKern),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
   if (attr != hipSuccess) return 0;
-  HGIN_TRACE("k_wsd_bf16<%d,%d%s>", NV, KV, PRO ? ",prelu_bwd_fused" : "");
-  kern<<<(unsigned)grid, 512, lds, s>>>(a, lda, b1, ldb1, b2, ldb2, k1, M, slab, ld_slab, pro);
+  HGIN_TRACE("%s<%d,%d%s>", name, nv, kv, fused ? ",prelu_bwd_fused" : "");
+  kKern<<<(unsigned)grid, 512, kLds, s>>>(a, lda, b1, ldb1, b2, ldb2, k1, M, slab, ld_slab, pro);
   return grid;
 }
 
-template <int NV, int KV, bool PRO = false>
-int64_t launch_wsd(const float* a, int64_t lda, const float* b1, int64_t ldb1, const float* b2, int64_t ldb2,
-                   int64_t k1, int64_t M, float* slab, int64_t ld_slab, int64_t grid, hipStream_t s,
+// (the streamed rows are DMA'd non-temporal: 1-3 % faster, profiles/r02/gemm_ws_bf16.txt)
+template <int NV, int KV, bool PRO = false, typename T>
+int64_t launch_wsd(const T* a, int64_t lda, const T* b1, int64_t ldb1, const T* b2, int64_t ldb2, int64_t k1,
+                   int64_t M, float* slab, int64_t ld_slab, int64_t grid, hipStream_t s,
                    const WsdPro& pro = WsdPro{}) {
-  // (the streamed rows are DMA'd non-temporal: 1-3 % faster, profiles/r02/gemm_ws_bf16.txt)
-  if constexpr (NV == 256 && KV == 256) {   // the GIN width: the pipelined form (k_wsd_f32 measured 3-8 % slower
-    auto kp = k_wsp_f32<PRO>;                 // here, profiles/r04/gpu_a/; removed from this shape in round 5)
-    constexpr int plds = WspF32Cfg::lds<PRO>();
-    static const hipError_t pattr = hipFuncSetAttribute(reinterpret_cast<const void*>(kp),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, plds);
-    if (pattr != hipSuccess) return 0;
-    HGIN_TRACE("k_wsp_f32<%d,%d%s>", NV, KV, PRO ? ",prelu_bwd_fused" : "");
-    kp<<<(unsigned)grid, 512, plds, s>>>(a, lda, b1, ldb1, b2, ldb2, k1, M, slab, ld_slab, pro);
-    return grid;
+  if constexpr (sizeof(T) == 2) {
+    using C = WsdCfg<NV, KV, PRO>;
+    return wsd_launch<k_wsd_bf16<NV, KV, PRO>, C::SLOT * C::NST>("k_wsd_bf16", NV, KV, PRO, a, lda, b1, ldb1, b2, ldb2, k1,
+                                                                 M, slab, ld_slab, grid, s, pro);
+  } else if constexpr (NV == 256 && KV == 256) {   // the GIN width: the pipelined form (k_wsd_f32 measured 3-8 % slower
+                                                   // here, profiles/r04/gpu_a/; removed from this shape in round 5)
+    return wsd_launch<k_wsp_f32<PRO>, WspF32Cfg::lds<PRO>()>("k_wsp_f32", NV, KV, PRO, a, lda, b1, ldb1, b2, ldb2, k1, M,
+                                                             slab, ld_slab, grid, s, pro);
   } else {
-    constexpr int lds = WsdF32Cfg<NV, KV, PRO>::LDS;
-    auto kern = k_wsd_f32<NV, KV, PRO>;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (attr != hipSuccess) return 0;
-    HGIN_TRACE("k_wsd_f32<%d,%d%s>", NV, KV, PRO ? ",prelu_bwd_fused" : "");
-    kern<<<(unsigned)grid, 512, lds, s>>>(a, lda, b1, ldb1, b2, ldb2, k1, M, slab, ld_slab, pro);
-    return grid;
+    return wsd_launch<k_wsd_f32<NV, KV, PRO>, WsdF32Cfg<NV, KV, PRO>::LDS>("k_wsd_f32", NV, KV, PRO, a, lda, b1, ldb1, b2,
+                                                                           ldb2, k1, M, slab, ld_slab, grid, s, pro);
   }
 }
 
-// One weight-stationary pass over output columns [c0, c0 + KV) of B = [b1 (k1 columns) | b2].
+// The two sources of output columns [c0, c0 + KV) of B = [b1 (k1 columns) | b2]: [c0, k1) from b1 (kk1 columns),
+// [max(c0, k1), c0 + KV) from b2.
+template <typename T>
+struct WsdColSrc {
+  const T* p1;
+  int64_t l1;
+  const T* p2;
+  int64_t l2;
+  int64_t kk1;
+};
+template <typename T>
+WsdColSrc<T> wsd_col_src(const T* b1, int64_t ldb1, int64_t k1, const T* b2, int64_t ldb2, int64_t c0, int64_t KV) {
+  WsdColSrc<T> c;
+  c.kk1 = k1 > c0 ? (k1 - c0 < KV ? k1 - c0 : KV) : 0;
+  c.p1 = c.kk1 > 0 ? b1 + c0 : b2;
+  c.l1 = c.kk1 > 0 ? ldb1 : ldb2;
+  c.p2 = c.kk1 < KV ? b2 + (c0 + c.kk1 - k1) : c.p1;
+  c.l2 = c.kk1 < KV ? ldb2 : c.l1;
+  return c;
+}
+
+// One weight-stationary pass over output columns [c0, c0 + KV).
 template <int NV, int KV, typename T>
 int64_t wsd_cols(const T* a, int64_t lda, const T* b1, int64_t ldb1, int64_t k1, const T* b2,
                  int64_t ldb2, int64_t c0, int64_t M, float* slab, int64_t ld_slab, int64_t grid, hipStream_t s) {
-  // the column block's two sources: [c0, k1) from b1, [max(c0, k1), c0 + KV) from b2
-  const int64_t kk1 = k1 > c0 ? (k1 - c0 < KV ? k1 - c0 : KV) : 0;
-  const T* p1 = kk1 > 0 ? b1 + c0 : b2;
-  const int64_t l1 = kk1 > 0 ? ldb1 : ldb2;
-  const T* p2 = kk1 < KV ? b2 + (c0 + kk1 - k1) : p1;
-  const int64_t l2 = kk1 < KV ? ldb2 : l1;
-  return launch_wsd<NV, KV>(a, lda, p1, l1, p2, l2, kk1, M, slab + c0, ld_slab, grid, s);
+  const WsdColSrc<T> c = wsd_col_src(b1, ldb1, k1, b2, ldb2, c0, KV);
+  return launch_wsd<NV, KV>(a, lda, c.p1, c.l1, c.p2, c.l2, c.kk1, M, slab + c0, ld_slab, grid, s);
 }
 
 // Column passes of the PReLU-fused dW: [0, KV) with the fold (forms + stores g_z, the partial sums), then for K = 512
@@ -1754,30 +1715,18 @@ template <typename T>
 int64_t wsd_pro_passes(const T* gy, int64_t ldgy, const T* b1, int64_t ldb1, int64_t k1, const T* b2, int64_t ldb2,
                        int64_t M, int64_t N, int64_t K, float* slab, int64_t grid, const WsdPro& pro, hipStream_t s) {
   const int64_t KV = (K == 512 && N == 256) ? 256 : K;
-  auto srcs = [&](int64_t c0, const T*& p1, int64_t& l1, const T*& p2, int64_t& l2, int64_t& kk1) {
-    kk1 = k1 > c0 ? (k1 - c0 < KV ? k1 - c0 : KV) : 0;
-    p1 = kk1 > 0 ? b1 + c0 : b2;
-    l1 = kk1 > 0 ? ldb1 : ldb2;
-    p2 = kk1 < KV ? b2 + (c0 + kk1 - k1) : p1;
-    l2 = kk1 < KV ? ldb2 : l1;
-  };
-  const T* p1;
-  const T* p2;
-  int64_t l1, l2, kk1;
-  srcs(0, p1, l1, p2, l2, kk1);
+  const WsdColSrc<T> c = wsd_col_src(b1, ldb1, k1, b2, ldb2, 0, KV);
   int64_t g;
-#define HGIN_PRO_PASS(NV, KVV) g = launch_wsd<NV, KVV, true>(gy, ldgy, p1, l1, p2, l2, kk1, M, slab, K, grid, s, pro);
+#define HGIN_PRO_PASS(NV, KVV) \
+  g = launch_wsd<NV, KVV, true>(gy, ldgy, c.p1, c.l1, c.p2, c.l2, c.kk1, M, slab, K, grid, s, pro);
   if (N == 256 && KV == 256) { HGIN_PRO_PASS(256, 256) }
   else if (N == 256) { HGIN_PRO_PASS(256, 128) }
   else if (KV == 512) { HGIN_PRO_PASS(128, 512) }
   else if (KV == 256) { HGIN_PRO_PASS(128, 256) }
   else { HGIN_PRO_PASS(128, 128) }
 #undef HGIN_PRO_PASS
-  if (!g || K != 512 || KV == 512) return g;
-  srcs(256, p1, l1, p2, l2, kk1);
-  const T* gz = static_cast<const T*>(pro.gz);
-  if (N == 256) return launch_wsd<256, 256>(gz, pro.ldgz, p1, l1, p2, l2, kk1, M, slab + 256, K, grid, s);
-  return launch_wsd<128, 256>(gz, pro.ldgz, p1, l1, p2, l2, kk1, M, slab + 256, K, grid, s);
+  if (!g || K != 512 || KV == 512) return g;   // (KV == 256 at K = 512 only for N = 256)
+  return wsd_cols<256, 256>(static_cast<const T*>(pro.gz), pro.ldgz, b1, ldb1, k1, b2, ldb2, 256, M, slab, K, grid, s);
 }
 
 // The PReLU-backward-fused weight-stationary dW (bf16, single column pass: N in {128, 256}, K in {128, 256}):
@@ -1786,35 +1735,20 @@ template <typename T>
 int64_t try_wsd_pro(const T* gy, int64_t ldgy, const T* b1, int64_t ldb1, int64_t k1, const T* b2, int64_t ldb2,
                     int64_t M, int64_t N, int64_t K, float* slab, int64_t max_slabs, const WsdPro& pro,
                     hipStream_t s) {
-  if constexpr (sizeof(T) == 4) {   // fp32 (split mode): N in {128, 256}, K in {128, 256, 512}
-    constexpr int64_t vw = 4;
-    if (!wsd_enabled() || !wsd_pro_enabled() || !gemm_split_enabled() || M < 1 || (N != 128 && N != 256) ||
-        (K != 128 && K != 256 && K != 512) || k1 % vw)
-      return 0;
-    auto ok = [](const void* p, int64_t ld) { return aligned16(p) && ld % vw == 0 && ld < (int64_t(1) << 24); };
-    if (!ok(gy, ldgy) || !ok(pro.z, pro.ldz) || !ok(pro.gz, pro.ldgz) || (k1 > 0 && !ok(b1, ldb1)) ||
-        (k1 < K && !ok(b2, ldb2)))
-      return 0;
-    int64_t grid = wsd_cus();
-    const int64_t nblk = ceil_div(M, (int64_t)16);
-    if (grid > nblk) grid = nblk;
-    if (grid > max_slabs) grid = max_slabs;
-    return wsd_pro_passes<T>(gy, ldgy, b1, ldb1, k1, b2, ldb2, M, N, K, slab, grid, pro, s);
-  } else {
-    constexpr int64_t vw = 8;
-    if (!wsd_enabled() || !wsd_pro_enabled() || M < 1 || (N != 128 && N != 256) ||
-        (K != 128 && K != 256 && K != 512) || k1 % vw)
-      return 0;
-    auto ok = [](const void* p, int64_t ld) { return aligned16(p) && ld % vw == 0 && ld < (int64_t(1) << 24); };
-    if (!ok(gy, ldgy) || !ok(pro.z, pro.ldz) || !ok(pro.gz, pro.ldgz) || (k1 > 0 && !ok(b1, ldb1)) ||
-        (k1 < K && !ok(b2, ldb2)))
-      return 0;
-    int64_t grid = wsd_cus();
-    const int64_t nblk = ceil_div(M, (int64_t)32);
-    if (grid > nblk) grid = nblk;
-    if (grid > max_slabs) grid = max_slabs;
-    return wsd_pro_passes<T>(gy, ldgy, b1, ldb1, k1, b2, ldb2, M, N, K, slab, grid, pro, s);
-  }
+  constexpr int64_t vw = 16 / sizeof(T);   // elements per 16-B chunk
+  if (!wsd_enabled() || !wsd_pro_enabled() || M < 1 || (N != 128 && N != 256) ||
+      (K != 128 && K != 256 && K != 512) || k1 % vw)
+    return 0;
+  if (sizeof(T) == 4 && !gemm_split_enabled()) return 0;   // the exact-f32 MFMA mode keeps the tiled kernel
+  auto ok = [](const void* p, int64_t ld) { return aligned16(p) && ld % vw == 0 && ld < (int64_t(1) << 24); };
+  if (!ok(gy, ldgy) || !ok(pro.z, pro.ldz) || !ok(pro.gz, pro.ldgz) || (k1 > 0 && !ok(b1, ldb1)) ||
+      (k1 < K && !ok(b2, ldb2)))
+    return 0;
+  int64_t grid = wsd_cus();
+  const int64_t nblk = ceil_div(M, (int64_t)(sizeof(T) == 2 ? 32 : 16));   // m rows per block
+  if (grid > nblk) grid = nblk;
+  if (grid > max_slabs) grid = max_slabs;
+  return wsd_pro_passes<T>(gy, ldgy, b1, ldb1, k1, b2, ldb2, M, N, K, slab, grid, pro, s);
 }
 
 template <typename T>

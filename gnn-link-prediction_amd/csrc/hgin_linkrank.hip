@@ -23,8 +23,6 @@
 namespace hgin {
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
 constexpr int kRankBK = 32;              // features per LDS stage
 constexpr int kRankRow = kRankBK + 4;    // LDS row stride in floats: the 16-B reads of 32 rows spread over the banks
 constexpr int kRankTile = 128;           // queries per workgroup = destinations per tile
@@ -114,12 +112,7 @@ __global__ __launch_bounds__(256, 2) void k_rank_sweep(const int64_t* __restrict
   load_stage(t_beg, 0);
   for (int64_t tile = t_beg; tile < t_end; ++tile) {
     f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.0f;
+    zero_acc(acc);
     for (int kc = 0; kc < nk; ++kc) {
       __syncthreads();   // the previous stage's reads are done
 #pragma unroll

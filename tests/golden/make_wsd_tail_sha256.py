@@ -1,6 +1,6 @@
 """Writes tests/golden/wsd_tail_sha256.json: SHA-256 of the outputs of every case of tests/test_gpu_wsd_tail.py
 (g_w, g_a, g_b, g_z of mlp_bwd_w and the plain gemm_tn on g_z), with the CU count they were recorded at.  Run on a
-GPU against a build of the commit whose bits are to be kept (the one before the dW loops were peeled):
+GPU against a build of the commit whose bits are to be kept (the parent of the change under test):
 
     python tests/golden/make_wsd_tail_sha256.py [--lib path/to/that/libhgin.so] [--out FILE]
 """
@@ -26,7 +26,7 @@ def main():
     spec = importlib.util.spec_from_file_location("wsd_tail", os.path.join(ROOT, "tests", "test_gpu_wsd_tail.py"))
     t = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(t)
-    cases = {f"{s}/{r}": t.case_hashes(s, r) for s in t.SHAPES for r in t.ROWS}
+    cases = t.all_case_hashes()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump({"cus": t.grid(), "cases": cases}, f, indent=1, sort_keys=True)
