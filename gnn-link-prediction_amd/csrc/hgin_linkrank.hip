@@ -18,39 +18,10 @@
 // are zeros on both operands (they add 0 * 0).  A given (query row, destination row) pair therefore gets bit-identical
 // scores in all three kernels and in every tile position: a copy of the positive's destination row is always counted
 // in n_equal.
-#include "hgin_common.h"
+#include "hgin_linkscore.h"   // the K order, ld_k4, mfma_k8, the tile constants and the split plan (shared with A16)
 
 namespace hgin {
 namespace {
-
-constexpr int kRankBK = 32;              // features per LDS stage
-constexpr int kRankRow = kRankBK + 4;    // LDS row stride in floats: the 16-B reads of 32 rows spread over the banks
-constexpr int kRankTile = 128;           // queries per workgroup = destinations per tile
-constexpr int kRankTargetBlocks = 512;   // two workgroups per CU on 256 CUs
-
-// four consecutive features k .. k + 3 of a row; features at or past F read as zero, nothing past F is touched
-template <bool VEC>
-__device__ __forceinline__ float4 ld_k4(const float* __restrict__ row, int k, int F) {
-  if constexpr (VEC) {   // F % 4 == 0 and 16-B aligned rows: k < F implies k + 3 < F
-    return k < F ? *reinterpret_cast<const float4*>(row + k) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  } else {
-    float4 v;
-    v.x = k < F ? row[k] : 0.0f;
-    v.y = k + 1 < F ? row[k + 1] : 0.0f;
-    v.z = k + 2 < F ? row[k + 2] : 0.0f;
-    v.w = k + 3 < F ? row[k + 3] : 0.0f;
-    return v;
-  }
-}
-
-__device__ __forceinline__ int64_t clamp_id(int64_t v, int64_t n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
-
-__device__ __forceinline__ void mfma_k8(f32x16& acc, const float4& a, const float4& b) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
-}
 
 // ---- the sweep ----------------------------------------------------------------------------------------------------
 // Workgroup = 4 waves as 2 x 2, each 64 destinations x 64 queries (2 x 2 MFMA blocks).  In an accumulator block lane
@@ -280,11 +251,9 @@ extern "C" int hgin_link_full_rank_f32(const int64_t* pos, int64_t n_pos, int64_
   float* thr = static_cast<float*>(ws);
   const bool vec = F % 4 == 0 && aligned16(z_src) && aligned16(z_dst) && ld_src % 4 == 0 && ld_dst % 4 == 0;
   const unsigned pair_grid = (unsigned)ceil_div(E, 128);
-  const int64_t n_qblocks = ceil_div(E, kRankTile), n_tiles = ceil_div(n_dst, kRankTile);
-  int64_t splits = ceil_div(kRankTargetBlocks, n_qblocks);
-  if (splits > n_tiles) splits = n_tiles;
-  const int64_t tiles_per_split = ceil_div(n_tiles, splits);
-  splits = ceil_div(n_tiles, tiles_per_split);
+  const SweepPlan plan = sweep_plan(E, n_dst);
+  const int64_t n_qblocks = plan.n_qblocks, n_tiles = plan.n_tiles, tiles_per_split = plan.tiles_per_split;
+  const int64_t splits = plan.splits;
   const unsigned sweep_grid = (unsigned)(n_qblocks * splits);
 
   int rc = memset_async(n_greater, 0, (size_t)E * sizeof(int32_t), s, what);

@@ -179,6 +179,8 @@ _SIGS = {
     "hgin_link_full_rank_workspace_size": ([_I64, _I64, _I64, ctypes.POINTER(_SZ)], _I32),
     "hgin_link_full_rank_f32": ([_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _P, _P, _P, _P, _SZ, _P],
                                 _I32),
+    "hgin_link_topk_workspace_size": ([_I64, _I64, _I64, _I64, ctypes.POINTER(_SZ)], _I32),
+    "hgin_link_topk_f32": ([_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _I64, _P, _P, _P, _SZ, _P], _I32),
     "hgin_aggregate_long_f32": ([_P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I32, _P, _I64, _P,
                                  _SZ, _P], _I32),
     "hgin_aggregate_long_bf16": ([_P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I32, _P, _I64, _P,
@@ -209,7 +211,7 @@ _SIGS = {
     "hgin_trace_enable": ([_I32], _I32),
     "hgin_trace_read": ([ctypes.c_char_p, _SZ], _SZ),
 }
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 def lib() -> ctypes.CDLL:

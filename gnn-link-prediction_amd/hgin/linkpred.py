@@ -17,6 +17,9 @@ the unfused pieces stay as the baseline the fused path is checked and timed agai
 Full evaluation (A15, not in the reference either): ``link_full_ranks`` / ``link_full_metrics`` /
 ``LinkPredictor.full_metrics`` rank every positive against *every* destination, optionally filtered by a set of known
 edges, on the fp32 matrix cores without materialising a score (csrc/hgin_linkrank.hip).
+
+Prediction (A16, not in the reference): ``link_topk`` / ``LinkPredictor.predict`` return the k best destinations of
+every query source, known edges left out, from the same sweep with a selecting epilogue (csrc/hgin_linktopk.hip).
 """
 from __future__ import annotations
 
@@ -329,6 +332,55 @@ def link_full_metrics(z_src: Tensor, z_dst: Tensor, pos: Tensor, known: Tensor =
     return full_metrics_from_ranks(*link_full_ranks(z_src, z_dst, pos, known))
 
 
+# ---------------------------------------------------------------------------------------------------
+# A16: top-K retrieval (NOT IN REFERENCE)
+# ---------------------------------------------------------------------------------------------------
+TOPK_MAX = 128
+
+
+def link_topk(z_src: Tensor, z_dst: Tensor, src: Tensor, k: int, known: Tensor = None):
+    """(idx int32 [Q, k], score float32 [Q, k]) (include/hgin.h A16): for every source ``src[q]`` (int64 [Q], repeats
+    allowed) the k best destinations c by <z_src[src[q]], z_dst[c]>, minus the c with (src[q], c) in ``known`` (an
+    edge index [2, M]; None: unfiltered), ordered by (score descending, index ascending); rows with fewer than k
+    candidates are padded with idx -1 / score -inf.  The scores are the bits ``link_full_ranks`` compares; no
+    [Q, n_dst] score matrix exists.  1 <= k <= 128.  No gradient."""
+    what = "link_topk"
+    for name, z in (("z_src", z_src), ("z_dst", z_dst)):
+        if z.dtype != torch.float32:
+            raise TypeError(f"{what}: {name} must be float32 (the fused link kernels are fp32 only), got {z.dtype}")
+        if z.dim() != 2:
+            raise RuntimeError(f"{what}: {name} must be [N, F]")
+    if z_src.size(1) != z_dst.size(1):
+        raise RuntimeError(f"{what}: embedding widths differ")
+    if src.dtype != torch.long or src.dim() != 1:
+        raise ValueError(f"{what}: src must be an int64 [Q] tensor, got {src.dtype} {tuple(src.shape)}")
+    ops.require_device(z_src, z_dst, src, known, what=what)
+    Q, k = int(src.numel()), int(k)
+    n_src, n_dst, F = int(z_src.size(0)), int(z_dst.size(0)), int(z_src.size(1))
+    if Q < 1 or Q >= 2**31 or not 1 <= k <= TOPK_MAX:
+        raise ValueError(f"{what}: need 1 <= Q < 2^31 and 1 <= k <= {TOPK_MAX} (Q = {Q}, k = {k})")
+    if F < 1 or n_src < 1 or n_dst < 1:
+        raise ValueError(f"{what}: embeddings need at least one row and one feature")
+    lo, hi = torch.stack([src.amin(), src.amax()]).tolist()   # the one host sync
+    if lo < 0 or hi >= n_src:
+        raise IndexError(f"{what}: src index out of range [0, {n_src})")
+    z_src, z_dst = ops._rowmajor(z_src.detach()), ops._rowmajor(z_dst.detach())
+    src, dev = src.contiguous(), z_src.device
+    rowptr = col = None
+    if known is not None:
+        rowptr, col = _known_csr(known, n_src, n_dst)
+    idx = torch.empty((Q, k), dtype=torch.int32, device=dev)
+    score = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(_lib.lib().hgin_link_topk_workspace_size(Q, n_dst, F, k, ctypes.byref(nbytes)),
+               "hgin_link_topk_workspace_size")
+    ws = ops._workspace(nbytes.value, dev)
+    _lib.call("hgin_link_topk_f32", ops._p(src), Q, n_src, n_dst, ops._p(z_src), z_src.stride(0), ops._p(z_dst),
+              z_dst.stride(0), F, ops._p(rowptr), ops._p(col), k, ops._p(idx), ops._p(score), ops._p(ws),
+              nbytes.value, ops._stream(idx))
+    return idx, score
+
+
 class LinkPredictor:
     """Link-prediction head over a model's node embeddings: ``relation`` = (src_type, name, dst_type), k uniform
     negatives per positive, dot-product decoder, BCE-with-logits (``sampled_link_loss``)."""
@@ -374,5 +426,23 @@ class LinkPredictor:
             with torch.no_grad():
                 z = self.model.encode(graph.x_dict(), graph.edge_index_dict())
                 return link_full_metrics(z[self.relation[0]], z[self.relation[2]], pos, known)
+        finally:
+            self.model.train(was_training)
+
+    def predict(self, graph, src: Tensor = None, k: int = 10, known: Tensor = None):
+        """``link_topk`` of the model's embeddings in eval mode, without gradients (the mode is restored): the k best
+        destinations of every source in ``src`` (default: every source node of the relation), minus ``known``
+        (default: the relation's own edges in ``graph``, so only new links are proposed)."""
+        if known is None:
+            known = graph.edge_index[self.relation]
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                z = self.model.encode(graph.x_dict(), graph.edge_index_dict())
+                z_src, z_dst = z[self.relation[0]], z[self.relation[2]]
+                if src is None:
+                    src = torch.arange(z_src.size(0), dtype=torch.long, device=z_src.device)
+                return link_topk(z_src, z_dst, src, k, known)
         finally:
             self.model.train(was_training)

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HGIN_ABI_VERSION 10
+#define HGIN_ABI_VERSION 11
 
 #define HGIN_OK 0
 #define HGIN_E_ARG (-1)        /* bad size / null pointer / unsupported combination */
@@ -487,6 +487,35 @@ int hgin_link_full_rank_f32(const int64_t* pos, int64_t n_pos, int64_t n_src, in
                             int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F,
                             const int32_t* known_rowptr, const int32_t* known_col, int32_t* n_greater,
                             int32_t* n_equal, int32_t* n_cand, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- A16: top-K link retrieval (NOT IN REFERENCE; build-defined, ABI 11) ---------------------------------------
+ * For query q (s = src[q]; src int64 [n_query], repeats allowed, the caller guarantees 0 <= s < n_src) and
+ * score(q, c) = <z_src[s], z_dst[c]>, the candidate set C(q) is every c in [0, n_dst) such that, when known_rowptr is
+ * given, (s, c) is not a known edge (there is no "own destination" here).  Row q of top_idx (int32 [n_query, k]) /
+ * top_score (float [n_query, k]) holds the min(k, |C(q)|) best candidates ordered by (score descending, index
+ * ascending) — a total order, so the result is unique —; the remaining slots hold idx = -1, score = -inf.
+ * known_rowptr int32 [n_src + 1] / known_col int32: as in A15, a CSR by source whose columns are sorted within each
+ * row (repeated columns are harmless, columns outside [0, n_dst) match nothing).  known_rowptr = NULL: unfiltered.
+ * Scores carry the bits of the A15 kernels: exact-fp32 matrix-core dot products (v_mfma_f32_32x32x2_f32), features in
+ * blocks of 8 in ascending order, inside a block in the pairs (0, 4), (1, 5), (2, 6), (3, 7), zeros past F.
+ * top_score[q, j] is bit for bit the threshold hgin_link_full_rank_f32 computes for the pair (s, top_idx[q, j]), and
+ * the output depends neither on how the destination range is split over workgroups nor on where a query sits in the
+ * batch.  Inputs are finite; with NaN or +-inf embeddings (or finite ones whose score overflows) the selection is
+ * unspecified (nothing out of bounds is touched).
+ * No [n_query, n_dst] object exists: the A15 sweep (128 queries x 128-destination tiles) compares the accumulators
+ * with one register threshold per lane and query column, the current k-th best of a private sorted list of k (score,
+ * index) entries per (query, split, wave row, lane half) kept in the workspace; a second kernel merges a query's
+ * 4 * splits lists under the total order.  No atomics, run-to-run identical.
+ * Workspace: hgin_link_topk_workspace_size = n_query * 4 * splits * (8 k + 4) bytes (each term rounded up to 256),
+ * splits = the A15 split count of (n_query, n_dst).  fp32 only; rows need no alignment (16-byte loads are used when F,
+ * both strides and both bases allow them).  1 <= n_query < 2^31, 1 <= n_src, n_dst < 2^31, 1 <= F < 2^24, ld >= F,
+ * 1 <= k <= 128 (k may exceed n_dst): HGIN_E_ARG before any launch otherwise, also for known_rowptr without
+ * known_col; HGIN_E_WORKSPACE for a workspace that is NULL or too small. */
+int hgin_link_topk_workspace_size(int64_t n_query, int64_t n_dst, int64_t F, int64_t k, size_t* bytes);
+int hgin_link_topk_f32(const int64_t* src, int64_t n_query, int64_t n_src, int64_t n_dst, const float* z_src,
+                       int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F, const int32_t* known_rowptr,
+                       const int32_t* known_col, int64_t k, int32_t* top_idx, float* top_score, void* ws,
+                       size_t ws_bytes, void* stream);
 
 /* ---- F4 widening: HetroGAT's graph attention (models.py:380-506, PyG 2.0.2 GATConv) ---------------------------
  * x_s / x_d: projected source / destination features [N, H * C] (row stride ld*), edges = the relation after
