@@ -10,6 +10,12 @@
 //   g_alpha_k = <g_out[i, h, :], x_s[j_k, h, :]>,  S_i = sum_k alpha_k g_alpha_k,  g_e_k = alpha_k (g_alpha_k - S_i),
 //   g_pre_k = g_e_k * (pre_k > 0 ? 1 : 0.2),  g_a_d[i, h] = sum_k g_pre_k,  g_x_d[i, h, :] = g_a_d[i, h] att_dst[h, :]
 //                                                                                  (k_gat_bwd_dst, CSR)
+//   sum_k g_e_k is 0 in exact arithmetic; in fp32 it is a residue R of S_i's rounding, carried mostly by the edge
+//   with the largest alpha.  With a peaked softmax g_a_d is itself a near-cancellation (sum_k |g_pre_k| << |S_i|)
+//   and R would dominate it, so g_a_d = sum_k g_pre_k - f'_top R with f'_top the leaky-relu slope factor of the
+//   largest-alpha edge (GatDstSum): that edge's share of the residue leaves, and g_a_d is accurate to
+//   eps sum_k |g_pre_k| — what autograd gets from PyG's softmax by routing the subtracted maximum's gradient to
+//   the argmax edge.  g_pre_k itself is stored unadjusted.
 //   g_x_s[j, h, :] = sum_k alpha_k g_out[i_k, h, :] + g_a_s[j, h] att_src[h, :],  g_a_s[j, h] = sum_k g_pre_k
 //                                                                                  (k_gat_bwd_src, CSC)
 //   g_att_src[h, c] = sum_j g_a_s[j, h] x_s[j, h, c], g_att_dst likewise, g_bias = sum_i g_out[i, :]  (k_gat_wsum)
@@ -74,6 +80,21 @@ __global__ __launch_bounds__(256) void k_gat_fwd(const int32_t* __restrict__ row
   }
 }
 
+// g_a_d = sum_k g_pre_k - f'_top sum_k g_e_k over a row's edges in order (see the header: the second sum is the
+// rounding residue of a sum that is 0 exactly; top = the first edge with the largest alpha).
+struct GatDstSum {
+  float gsum = 0.0f, gesum = 0.0f, atop = -1.0f, ftop = 0.0f;
+  __device__ __forceinline__ void add(float al, float ge, float gp, float fp) {
+    gsum = __fadd_rn(gsum, gp);
+    gesum = __fadd_rn(gesum, ge);
+    if (al > atop) {
+      atop = al;
+      ftop = fp;
+    }
+  }
+  __device__ __forceinline__ float result() const { return __fsub_rn(gsum, __fmul_rn(ftop, gesum)); }
+};
+
 // g_pre (per CSR edge and head) and g_a_d; g_x_d = g_a_d att_dst when requested.
 __global__ __launch_bounds__(256) void k_gat_bwd_dst(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                      int64_t n_dst, int H, int C, const float* __restrict__ xs,
@@ -97,15 +118,17 @@ __global__ __launch_bounds__(256) void k_gat_bwd_dst(const int32_t* __restrict__
     S = __fadd_rn(S, __fmul_rn(alpha[(int64_t)k * H + h], ga));
   }
   const float adv = ad ? ad[t] : 0.0f;
-  float gsum = 0.0f;
+  GatDstSum acc;
   for (int k = rb; k < re; ++k) {
     const int64_t q = (int64_t)k * H + h;
-    const float ge = __fmul_rn(alpha[q], __fsub_rn(g_pre[q], S));
+    const float al = alpha[q];
+    const float ge = __fmul_rn(al, __fsub_rn(g_pre[q], S));
     const float pre = __fadd_rn(as[(int64_t)col[k] * H + h], adv);
     const float gp = pre > 0.0f ? ge : __fmul_rn(ge, slope);
     g_pre[q] = gp;
-    gsum = __fadd_rn(gsum, gp);
+    acc.add(al, ge, gp, pre > 0.0f ? 1.0f : slope);
   }
+  const float gsum = acc.result();
   if (g_ad) g_ad[t] = gsum;
   if (g_xd) {
     float* gx = g_xd + i * ldgxd + (int64_t)h * C;
@@ -462,7 +485,8 @@ __global__ __launch_bounds__(256) void k_gat_attn_w(const int32_t* __restrict__ 
 // Backward, destination side.  Phase A (column lanes, CSR order, U rows in flight): g_alpha_k = <g_out[i, h, :],
 // x_s[j_k, h, :]> (each lane its 4 products, then the head's C / 4 lanes), S_h = sum_k alpha_k g_alpha_k; the head's
 // first lane stores g_alpha_k.  Phase B (the head's first lane, CSR order): g_pre_k = leaky'(pre_k) alpha_k
-// (g_alpha_k - S_h) over its own stores, g_a_d = sum_k g_pre_k; g_x_d = g_a_d att_dst on the column lanes.  The row's
+// (g_alpha_k - S_h) over its own stores, g_a_d = sum_k g_pre_k less the residue term (GatDstSum); g_x_d = g_a_d att_dst
+// on the column lanes.  The row's
 // first G edge sources come in one coalesced load and reach the lanes by ds_bpermute (k_gat_attn_w's scheme), so a
 // batch of U edges costs one dependent round trip (both phases run their loops on every lane of the group: the
 // shuffles need them).
@@ -516,7 +540,7 @@ __global__ __launch_bounds__(256) void k_gat_bwd_dst_w(const int32_t* __restrict
       }
     }
   }
-  float gsum = 0.0f;
+  GatDstSum dsum;
   const float adv = first && ad ? ad[i * H + hq] : 0.0f;
   for (int k0 = 0; k0 < deg; k0 += U) {   // U edges' operands loaded together
     float al[U], ga[U], av[U];
@@ -538,10 +562,11 @@ __global__ __launch_bounds__(256) void k_gat_bwd_dst_w(const int32_t* __restrict
         const float pre = __fadd_rn(av[u], adv);
         const float gp = pre > 0.0f ? ge : __fmul_rn(ge, slope);
         g_pre[(int64_t)(rb + k0 + u) * H + hq] = gp;
-        gsum = __fadd_rn(gsum, gp);
+        dsum.add(al[u], ge, gp, pre > 0.0f ? 1.0f : slope);
       }
     }
   }
+  float gsum = dsum.result();
   if (first && g_ad) g_ad[i * H + hq] = gsum;
   if (g_xd) {
     const int srcl = lane_on ? hq * (C / 4) : gl;

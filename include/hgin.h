@@ -526,7 +526,9 @@ int hgin_link_topk_f32(const int64_t* src, int64_t n_query, int64_t n_src, int64
  *                         (exp(e - max) / (sum + 1e-16), PyG's softmax); out[i, h, :] = sum_k alpha x_s[j_k, h, :]
  *                         + bias [+ accum].  a_d, bias, accum may be NULL.
  *   hgin_gat_bwd_dst_f32: g_pre[k, h] = d loss / d (a_s[j_k, h] + a_d[i, h]) (softmax + leaky_relu backward),
- *                         g_ad[i, h] = sum_k g_pre, g_xd[i, h, :] = g_ad[i, h] att_dst[h, :] (g_ad / g_xd may be NULL)
+ *                         g_ad[i, h] = sum_k g_pre (less the rounding residue of the softmax backward's zero sum, so
+ *                         accurate to eps sum_k |g_pre|), g_xd[i, h, :] = g_ad[i, h] att_dst[h, :] (g_ad / g_xd may be
+ *                         NULL)
  *   hgin_gat_bwd_src_f32: g_as[j, h] = sum_k g_pre, g_xs[j, h, :] = sum_k alpha g_out[i_k, h, :] + g_as att_src[h, :]
  *   hgin_gat_wsum_f32:    out[h * C + c] = sum_n w[n, h] x[n, h * C + c] (w NULL: 1), fixed 256-row blocks in order;
  *                         workspace: hgin_gat_wsum_workspace_size. */
