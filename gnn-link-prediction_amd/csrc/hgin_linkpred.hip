@@ -179,13 +179,32 @@ __device__ __forceinline__ uint32_t word_of(const U4& x, uint32_t w) {
   return w == 0 ? x.x : (w == 1 ? x.y : (w == 2 ? x.z : x.w));
 }
 
-template <int VEC, int G, bool ONE, bool RANK>
+// A17: the objective of the loss epilogue (include/hgin.h HGIN_LINK_OBJ_*).  kObjBce is A13's finish_pair, untouched.
+constexpr int kObjBce = 0, kObjSoftmax = 1, kObjBpr = 2, kObjSelfAdv = 3;
+
+// sigmoid(x) and softplus(x) from the one exp(-|x|), as finish_pair forms them
+__device__ __forceinline__ void sig_softplus(float x, float& sig, float& sp) {
+  const float ex = expf(-fabsf(x));
+  sig = (x >= 0.0f ? 1.0f : ex) / (1.0f + ex);
+  sp = __fadd_rn(fmaxf(x, 0.0f), log1pf(ex));
+}
+
+// the softmax argument of a score: scale * s kept finite, so that max / subtract never meet inf - inf
+__device__ __forceinline__ float soft_arg(float s, float scale) {
+  return fminf(fmaxf(__fmul_rn(s, scale), -3.402823466e38f), 3.402823466e38f);
+}
+
+// Weights by objective (launch_link_fwd): bce w_pos = 0.5 / E, w_neg = 0.5 / (E k); softmax w_pos = 1 / E (loss),
+// w_neg = 1 / (tau E) (coefficients), xscale = 1 / tau; bpr w_neg = 1 / (E k); selfadv w_pos = 0.5 / E, xscale = alpha.
+template <int VEC, int G, bool ONE, bool RANK, int OBJ>
 __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ pos, int64_t E, int k, uint64_t seed,
                                                   uint64_t offset, uint32_t n_dst, const float* __restrict__ zs,
                                                   int64_t lds, const float* __restrict__ zd, int64_t ldd, int F,
-                                                  float w_pos, float w_neg, float* __restrict__ coef,
+                                                  float w_pos, float w_neg, float xscale, float* __restrict__ coef,
                                                   int64_t* __restrict__ neg, float* __restrict__ partial,
                                                   int32_t* __restrict__ n_gt, int32_t* __restrict__ n_eq) {
+  constexpr bool TWO_PHASE = !RANK && (OBJ == kObjSoftmax || OBJ == kObjSelfAdv);
+  constexpr bool POS_IS_SUM = !RANK && (OBJ == kObjSoftmax || OBJ == kObjBpr);
   constexpr int EPW = 64 / G;   // edges per wave
   const int lane = threadIdx.x & 63;
   const int grp = lane / G, gl = lane % G;
@@ -226,6 +245,58 @@ __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ po
     const uint64_t base = offset + (uint64_t)e * (uint64_t)k;
     float s_pos = 0.0f;
     int gt = 0, eq = 0;
+    // A17 state of this positive: online (max, sum - 1) of the softmax arguments (softmax: pairs 0 .. k, selfadv: the
+    // negatives), identical in every lane of the group, and this lane's sum of the negatives' coefficients
+    float m_run = -INFINITY, S_run = 0.0f, c_neg = 0.0f;
+    // A17, batch loop: bpr finishes negative t against s_pos; the two-phase objectives park the raw score in the
+    // pair's coefficient slot (selfadv's positive is independent of the normaliser and is finished here, as bce's)
+    auto first_pass = [&](int t, float s, int64_t idm) {
+      if (t == 0) {
+        if constexpr (OBJ == kObjSelfAdv) {
+          float sig, sp;
+          sig_softplus(-s, sig, sp);
+          lsum = __fadd_rn(lsum, __fmul_rn(w_pos, sp));
+          coef[e] = __fmul_rn(w_pos, -sig);
+        }
+        return;
+      }
+      const int64_t q = e * (int64_t)k + (t - 1);
+      neg[q] = s0;
+      neg[nk + q] = idm;
+      if constexpr (OBJ == kObjBpr) {
+        float sig, sp;
+        sig_softplus(__fsub_rn(s, s_pos), sig, sp);
+        lsum = __fadd_rn(lsum, __fmul_rn(w_neg, sp));
+        const float c = __fmul_rn(w_neg, sig);
+        coef[E + q] = c;
+        c_neg = __fadd_rn(c_neg, c);
+      } else {
+        coef[E + q] = s;
+      }
+    };
+    // A17, after the last batch: the lane that parked pair t's score reads it back and finishes the pair
+    auto second_pass = [&](int t) {
+      if (t == 0) {
+        if constexpr (OBJ == kObjSoftmax)   // logsumexp - x_0 = (max - x_0) + log(1 + the other terms)
+          lsum = __fadd_rn(lsum, __fmul_rn(w_pos, __fadd_rn(__fsub_rn(m_run, soft_arg(s_pos, xscale)),
+                                                           log1pf(S_run))));
+        return;
+      }
+      const int64_t q = e * (int64_t)k + (t - 1);
+      const float s = coef[E + q];
+      const float p = expf(__fsub_rn(soft_arg(s, xscale), m_run)) / __fadd_rn(1.0f, S_run);
+      if constexpr (OBJ == kObjSoftmax) {
+        const float c = __fmul_rn(w_neg, p);
+        coef[E + q] = c;
+        c_neg = __fadd_rn(c_neg, c);
+      } else {
+        float sig, sp;
+        sig_softplus(s, sig, sp);
+        const float wp = __fmul_rn(w_pos, p);
+        lsum = __fadd_rn(lsum, __fmul_rn(wp, sp));
+        coef[E + q] = __fmul_rn(wp, sig);
+      }
+    };
     for (int t0 = 0; t0 <= k; t0 += kInFlight) {
       // destination ids of pairs t0 .. t0 + 3: their counters span at most two Philox blocks
       const int tf = t0 == 0 ? 1 : t0;                       // first negative of the batch (tf <= k)
@@ -289,6 +360,37 @@ __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ po
           if (t == 0) s_pos = sc[u];
           else if (t <= k) { gt += sc[u] > s_pos; eq += sc[u] == s_pos; }
         }
+      } else if constexpr (OBJ != kObjBce) {
+        // after the shuffles every lane of the group holds the batch's four scores
+        if (t0 == 0) s_pos = sc[0];
+        if constexpr (TWO_PHASE) {
+          // online normaliser, pairs in order; t0, k are uniform, so masked pairs (t > k) are skipped by all lanes
+          // S_run leaves out the maximum's own term exp(0) = 1, so that log1p(S_run) keeps a loss far below 1.  One
+          // exp per pair serves both cases: a new maximum turns the old one into a term and rescales by exp(m - x),
+          // anything else adds exp(x - m).  First pair: m = -inf, (0 + 1) * exp(-inf) = 0.
+          constexpr int T_MIN = OBJ == kObjSoftmax ? 0 : 1;
+#pragma unroll
+          for (int u = 0; u < kInFlight; ++u)
+            if (t0 + u >= T_MIN && t0 + u <= k) {
+              const float x = soft_arg(sc[u], xscale);
+              const bool up = x > m_run;
+              const float ex = expf(-fabsf(__fsub_rn(x, m_run)));
+              S_run = up ? __fmul_rn(__fadd_rn(S_run, 1.0f), ex) : __fadd_rn(S_run, ex);
+              m_run = up ? x : m_run;
+            }
+        }
+        if constexpr (G >= kInFlight) {
+          float s = sc[0];
+          int64_t idm = id[0];
+#pragma unroll
+          for (int u = 1; u < kInFlight; ++u)
+            if (gl == u) { s = sc[u]; idm = id[u]; }
+          if (valid && gl < kInFlight && t0 + gl <= k) first_pass(t0 + gl, s, idm);
+        } else {
+#pragma unroll
+          for (int u = 0; u < kInFlight; ++u)
+            if (writer && t0 + u <= k) first_pass(t0 + u, sc[u], id[u]);
+        }
       } else if constexpr (G >= kInFlight) {
         // every lane holds the four scores: lane u of the group finishes pair t0 + u (one exp / log1p per batch
         // instead of four in a row on lane 0, and the group's stores fall side by side)
@@ -307,6 +409,27 @@ __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ po
     if (RANK && writer) {
       n_gt[e] = gt;
       n_eq[e] = eq;
+    }
+    if constexpr (TWO_PHASE) {
+      // the (t0, u) -> lane mapping of the batch loop again: every lane reads the slots it wrote itself
+      if constexpr (G >= kInFlight) {
+        if (valid && gl < kInFlight)
+          for (int t = gl; t <= k; t += kInFlight) second_pass(t);
+      } else {
+        if (writer)
+          for (int t = 0; t <= k; ++t) second_pass(t);
+      }
+    }
+    if constexpr (POS_IS_SUM) {
+      // the positive's coefficient = -(sum of its negatives' stored coefficients): lanes 0 .. 3 in order.  For softmax
+      // that is (p_0 - 1) / (tau E) without the cancellation near p_0 = 1.
+      float c = c_neg;
+      if constexpr (G >= kInFlight) {
+        c = __shfl(c_neg, 0, G);
+#pragma unroll
+        for (int u = 1; u < kInFlight; ++u) c = __fadd_rn(c, __shfl(c_neg, u, G));
+      }
+      if (writer) coef[e] = -c;
     }
   }
   if (!RANK) {
@@ -581,15 +704,27 @@ int link_common_checks(const char* what, const int64_t* pos, int64_t E, int64_t 
   return HGIN_OK;
 }
 
-template <bool RANK>
+template <bool RANK, int OBJ = kObjBce>
 void launch_link_fwd(const LinkShape& sh, hipStream_t s, const int64_t* pos, int64_t E, int k, uint64_t seed,
                      uint64_t offset, uint32_t n_dst, const float* z_src, int64_t ld_src, const float* z_dst,
-                     int64_t ld_dst, int F, float* coef, int64_t* neg, float* partial, int32_t* n_gt, int32_t* n_eq) {
-  const float w_pos = (float)(0.5 / (double)E), w_neg = (float)(0.5 / ((double)E * (double)k));
-  HGIN_TRACE("k_link_fwd<%d,%d,%s,%s>", sh.vec ? 4 : 1, sh.g, sh.one ? "ONE" : "LOOP", RANK ? "RANK" : "LOSS");
+                     int64_t ld_dst, int F, float* coef, int64_t* neg, float* partial, int32_t* n_gt, int32_t* n_eq,
+                     float param = 0.0f) {
+  float w_pos = (float)(0.5 / (double)E), w_neg = (float)(0.5 / ((double)E * (double)k)), xscale = 0.0f;
+  if (OBJ == kObjSoftmax) {
+    w_pos = (float)(1.0 / (double)E);
+    w_neg = (float)(1.0 / ((double)param * (double)E));
+    xscale = (float)(1.0 / (double)param);
+  } else if (OBJ == kObjBpr) {
+    w_neg = (float)(1.0 / ((double)E * (double)k));
+  } else if (OBJ == kObjSelfAdv) {
+    xscale = param;
+  }
+  constexpr const char* kEpilogue[] = {"LOSS", "SOFTMAX", "BPR", "SELFADV"};
+  HGIN_TRACE("k_link_fwd<%d,%d,%s,%s>", sh.vec ? 4 : 1, sh.g, sh.one ? "ONE" : "LOOP", RANK ? "RANK" : kEpilogue[OBJ]);
 #define HGIN_LINK_FWD(VEC_, G_, ONE_)                                                                              \
-  k_link_fwd<VEC_, G_, ONE_, RANK><<<sh.grid, 256, 0, s>>>(pos, E, k, seed, offset, n_dst, z_src, ld_src, z_dst,   \
-                                                           ld_dst, F, w_pos, w_neg, coef, neg, partial, n_gt, n_eq)
+  k_link_fwd<VEC_, G_, ONE_, RANK, OBJ><<<sh.grid, 256, 0, s>>>(pos, E, k, seed, offset, n_dst, z_src, ld_src,     \
+                                                                z_dst, ld_dst, F, w_pos, w_neg, xscale, coef, neg, \
+                                                                partial, n_gt, n_eq)
   if (sh.vec) {
     if (!sh.one) HGIN_LINK_FWD(4, 64, false);
     else HGIN_G_SWITCH(sh.g, HGIN_LINK_FWD(4, G, true))
@@ -633,6 +768,47 @@ extern "C" int hgin_link_loss_fwd_f32(const int64_t* pos, int64_t n_pos, int64_t
   HGIN_TRACE("k_link_loss_sum");
   k_link_loss_sum<<<1, 256, 0, s>>>(partial, (int)sh.grid, loss);
   return check_launch("hgin_link_loss_fwd_f32");
+}
+
+extern "C" int hgin_link_loss_fwd_obj_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64_t seed, uint64_t offset,
+                                          int64_t n_dst, const float* z_src, int64_t ld_src, const float* z_dst,
+                                          int64_t ld_dst, int64_t F, float* coef, int64_t* neg, float* loss,
+                                          void* workspace, size_t workspace_bytes, int32_t objective, float param,
+                                          void* stream) {
+  const char* what = "hgin_link_loss_fwd_obj_f32";
+  const int rc = link_common_checks(what, pos, n_pos, k, n_dst, z_src, ld_src, z_dst, ld_dst, F);
+  if (rc != HGIN_OK) return rc;
+  HGIN_ARG_CHECK(coef != nullptr, "%s: coef NULL", what);
+  HGIN_ARG_CHECK(neg != nullptr, "%s: neg NULL", what);
+  HGIN_ARG_CHECK(loss != nullptr, "%s: loss NULL", what);
+  HGIN_ARG_CHECK(objective >= kObjBce && objective <= kObjSelfAdv, "%s: objective = %d must be in [0, 3]", what,
+                 (int)objective);
+  HGIN_ARG_CHECK(objective != kObjSoftmax || (std::isfinite(param) && param > 0.0f),
+                 "%s: temperature = %g must be finite and > 0", what, (double)param);
+  HGIN_ARG_CHECK(objective != kObjSelfAdv || (std::isfinite(param) && param >= 0.0f),
+                 "%s: alpha = %g must be finite and >= 0", what, (double)param);
+  if (workspace == nullptr || workspace_bytes < (size_t)kLinkMaxGrid * sizeof(float)) {
+    set_error("%s: workspace %zu bytes < required %zu", what, workspace_bytes, (size_t)kLinkMaxGrid * sizeof(float));
+    return HGIN_E_WORKSPACE;
+  }
+  if (objective == kObjBce)
+    return hgin_link_loss_fwd_f32(pos, n_pos, k, seed, offset, n_dst, z_src, ld_src, z_dst, ld_dst, F, coef, neg, loss,
+                                  workspace, workspace_bytes, stream);
+  hipStream_t s = as_stream(stream);
+  const LinkShape sh = link_shape(n_pos, F, z_src, ld_src, z_dst, ld_dst);
+  float* partial = static_cast<float*>(workspace);
+#define HGIN_LINK_OBJ(OBJ_)                                                                                          \
+  launch_link_fwd<false, OBJ_>(sh, s, pos, n_pos, (int)k, seed, offset, (uint32_t)n_dst, z_src, ld_src, z_dst, ld_dst, \
+                               (int)F, coef, neg, partial, nullptr, nullptr, param)
+  if (objective == kObjSoftmax) HGIN_LINK_OBJ(kObjSoftmax);
+  else if (objective == kObjBpr) HGIN_LINK_OBJ(kObjBpr);
+  else HGIN_LINK_OBJ(kObjSelfAdv);
+#undef HGIN_LINK_OBJ
+  const int rc2 = check_launch(what);
+  if (rc2 != HGIN_OK) return rc2;
+  HGIN_TRACE("k_link_loss_sum");
+  k_link_loss_sum<<<1, 256, 0, s>>>(partial, (int)sh.grid, loss);
+  return check_launch(what);
 }
 
 extern "C" int hgin_link_rank_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64_t seed, uint64_t offset,

@@ -14,6 +14,10 @@ deterministic store-and-sum backward; ``link_ranks`` / ``link_metrics`` evaluate
 epilogue; ``LinkPredictor`` puts them behind ``model.encode`` (hgin/train.py::link_train_step).  ``link_loss`` and
 the unfused pieces stay as the baseline the fused path is checked and timed against (tools/bench_linkpred.py).
 
+Objectives (A17, not in the reference): ``sampled_link_loss`` / ``link_loss`` / ``LinkPredictor`` take ``objective`` =
+"bce" (default), "softmax", "bpr" or "selfadv"; in the fused path each is another forward epilogue that writes the same
+coefficient array, so the backward is shared.
+
 Full evaluation (A15, not in the reference either): ``link_full_ranks`` / ``link_full_metrics`` /
 ``LinkPredictor.full_metrics`` rank every positive against *every* destination, optionally filtered by a set of known
 edges, on the fp32 matrix cores without materialising a score (csrc/hgin_linkrank.hip).
@@ -24,6 +28,7 @@ every query source, known edges left out, from the same sweep with a selecting e
 from __future__ import annotations
 
 import ctypes
+import math
 
 import torch
 from torch import Tensor
@@ -95,13 +100,44 @@ def dot_decode(z_src: Tensor, z_dst: Tensor, pairs: Tensor) -> Tensor:
     return _DotDecodeFn.apply(z_src, z_dst, pairs, graph)
 
 
-def link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0) -> Tensor:
-    """BCE-with-logits over positives and k uniform negatives per positive."""
+# the objectives of the sampled link loss (include/hgin.h A17), in the order of the C ABI's codes
+LINK_OBJECTIVES = ("bce", "softmax", "bpr", "selfadv")
+
+
+def _objective(what: str, objective, temperature, alpha):
+    """(code, param) of the C ABI for a checked objective; ValueError for anything else, before any launch."""
+    if objective not in LINK_OBJECTIVES:
+        raise ValueError(f"{what}: unknown objective {objective!r} (one of {', '.join(LINK_OBJECTIVES)})")
+    temperature, alpha = float(temperature), float(alpha)
+    if not (math.isfinite(temperature) and temperature > 0.0):
+        raise ValueError(f"{what}: temperature must be finite and > 0, got {temperature}")
+    if not (math.isfinite(alpha) and alpha >= 0.0):
+        raise ValueError(f"{what}: alpha must be finite and >= 0, got {alpha}")
+    code = LINK_OBJECTIVES.index(objective)
+    return code, {1: temperature, 3: alpha}.get(code, 0.0)
+
+
+def link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0, objective: str = "bce",
+              temperature: float = 1.0, alpha: float = 1.0) -> Tensor:
+    """The unfused sampled link loss over positives and k uniform negatives per positive: ``objective`` "bce"
+    (BCE-with-logits, the default), "softmax", "bpr" or "selfadv" (include/hgin.h A17), as torch ops on the two
+    ``dot_decode`` score vectors."""
+    code, param = _objective("link_loss", objective, temperature, alpha)
     neg = negative_edges(pos, z_dst.size(0), k, seed, offset)
     s_pos = dot_decode(z_src, z_dst, pos)
     s_neg = dot_decode(z_src, z_dst, neg)
-    bce = torch.nn.functional.binary_cross_entropy_with_logits
-    return bce(s_pos, torch.ones_like(s_pos)) * 0.5 + bce(s_neg, torch.zeros_like(s_neg)) * 0.5
+    fn = torch.nn.functional
+    if code == 0:
+        bce = fn.binary_cross_entropy_with_logits
+        return bce(s_pos, torch.ones_like(s_pos)) * 0.5 + bce(s_neg, torch.zeros_like(s_neg)) * 0.5
+    s_neg = s_neg.reshape(-1, int(k))
+    if code == 1:
+        x = torch.cat([s_pos.unsqueeze(1), s_neg], 1) / param
+        return (torch.logsumexp(x, 1) - x[:, 0]).mean()
+    if code == 2:
+        return fn.softplus(s_neg - s_pos.unsqueeze(1)).mean()
+    p = torch.softmax(param * s_neg, 1).detach()
+    return 0.5 * (fn.softplus(-s_pos) + (p * fn.softplus(s_neg)).sum(1)).mean()
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -140,7 +176,8 @@ def _side_stream(device) -> "torch.cuda.Stream":
 
 class _SampledLinkLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, z_src, z_dst, pos, graph: ops.RelationGraph, k: int, seed: int, offset: int):
+    def forward(ctx, z_src, z_dst, pos, graph: ops.RelationGraph, k: int, seed: int, offset: int, objective: int = 0,
+                param: float = 0.0):
         E, F, dev = int(pos.size(1)), int(z_src.size(1)), z_src.device
         coef = torch.empty(E * (1 + k), dtype=torch.float32, device=dev)
         neg = torch.empty((2, E * k), dtype=torch.int64, device=dev)
@@ -148,9 +185,15 @@ class _SampledLinkLossFn(torch.autograd.Function):
         nbytes = ctypes.c_size_t(0)
         _lib.check(_lib.lib().hgin_link_loss_workspace_size(E, ctypes.byref(nbytes)), "hgin_link_loss_workspace_size")
         ws = ops._workspace(nbytes.value, dev)
-        _lib.call("hgin_link_loss_fwd_f32", ops._p(pos), E, k, int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
-                  int(z_dst.size(0)), ops._p(z_src), z_src.stride(0), ops._p(z_dst), z_dst.stride(0), F, ops._p(coef),
-                  ops._p(neg), ops._p(loss), ops._p(ws), nbytes.value, ops._stream(loss))
+        if objective == 0:
+            _lib.call("hgin_link_loss_fwd_f32", ops._p(pos), E, k, int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
+                      int(z_dst.size(0)), ops._p(z_src), z_src.stride(0), ops._p(z_dst), z_dst.stride(0), F,
+                      ops._p(coef), ops._p(neg), ops._p(loss), ops._p(ws), nbytes.value, ops._stream(loss))
+        else:   # another epilogue writes the same coef / neg (A17): the backward below serves every objective
+            _lib.call("hgin_link_loss_fwd_obj_f32", ops._p(pos), E, k, int(seed) & (2**64 - 1),
+                      int(offset) & (2**64 - 1), int(z_dst.size(0)), ops._p(z_src), z_src.stride(0), ops._p(z_dst),
+                      z_dst.stride(0), F, ops._p(coef), ops._p(neg), ops._p(loss), ops._p(ws), nbytes.value,
+                      objective, param, ops._stream(loss))
         ctx.graph, ctx.k = graph, k
         ctx.save_for_backward(coef, neg, z_src, z_dst)
         return loss.reshape(())
@@ -198,16 +241,20 @@ class _SampledLinkLossFn(torch.autograd.Function):
             _lib.call("hgin_link_loss_bwd_dst_f32", ops._p(csr.rowptr), ops._p(csr.col), ops._p(csr.perm),
                       ops._p(nrow), ops._p(ncol), ops._p(nperm), n_dst, E, ops._p(g), ops._p(coef), ops._p(z_src),
                       z_src.stride(0), F, ops._p(g_dst), g_dst.stride(0), ops._stream(g))
-        return g_src, g_dst, None, None, None, None, None
+        return g_src, g_dst, None, None, None, None, None, None, None
 
 
-def sampled_link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0) -> Tensor:
-    """``link_loss`` in fused form (include/hgin.h A13): the same pairs (``negative_edges(pos, n_dst, k, seed,
+def sampled_link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0,
+                      objective: str = "bce", temperature: float = 1.0, alpha: float = 1.0) -> Tensor:
+    """``link_loss`` in fused form (include/hgin.h A13 / A17): the same pairs (``negative_edges(pos, n_dst, k, seed,
     offset)``) and the same loss, one forward pass that draws the negatives in the kernel and reads every source
     row once, and a deterministic store-and-sum backward (static CSC / CSR of ``pos`` + one sort of the step's
-    negatives).  Returns a scalar; fp32 embeddings only."""
+    negatives).  ``objective``: "bce" (default), "softmax" (InfoNCE over the positive and its k negatives at
+    ``temperature``), "bpr" (pairwise) or "selfadv" (BCE with the negatives weighted by a detached
+    softmax(``alpha`` * score)); only the forward epilogue differs.  Returns a scalar; fp32 embeddings only."""
+    code, param = _objective("sampled_link_loss", objective, temperature, alpha)
     z_src, z_dst, pos, graph, _, k = _link_operands("sampled_link_loss", z_src, z_dst, pos, k)
-    return _SampledLinkLossFn.apply(z_src, z_dst, pos, graph, k, int(seed), int(offset))
+    return _SampledLinkLossFn.apply(z_src, z_dst, pos, graph, k, int(seed), int(offset), code, param)
 
 
 def link_ranks(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0):
@@ -383,12 +430,17 @@ def link_topk(z_src: Tensor, z_dst: Tensor, src: Tensor, k: int, known: Tensor =
 
 class LinkPredictor:
     """Link-prediction head over a model's node embeddings: ``relation`` = (src_type, name, dst_type), k uniform
-    negatives per positive, dot-product decoder, BCE-with-logits (``sampled_link_loss``)."""
+    negatives per positive, dot-product decoder, and the training objective of ``sampled_link_loss`` ("bce" by
+    default; "softmax" with ``temperature``, "bpr", "selfadv" with ``alpha``).  The objective only shapes ``loss``;
+    ``metrics``, ``full_metrics`` and ``predict`` do not depend on it."""
 
-    def __init__(self, model, relation, k: int, seed: int):
+    def __init__(self, model, relation, k: int, seed: int, objective: str = "bce", temperature: float = 1.0,
+                 alpha: float = 1.0):
         if not hasattr(model, "encode"):
             raise TypeError("LinkPredictor: the model has no encode(x_dict, edge_index_dict)")
+        _objective("LinkPredictor", objective, temperature, alpha)
         self.model, self.relation, self.k, self.seed = model, tuple(relation), int(k), int(seed)
+        self.objective, self.temperature, self.alpha = objective, float(temperature), float(alpha)
 
     def _pos(self, graph, pos):
         return graph.edge_index[self.relation] if pos is None else pos
@@ -399,7 +451,8 @@ class LinkPredictor:
         pos = self._pos(graph, pos)
         z = self.model.encode(graph.x_dict(), graph.edge_index_dict())
         offset = int(step) * int(pos.size(1)) * self.k
-        return sampled_link_loss(z[self.relation[0]], z[self.relation[2]], pos, self.k, self.seed, offset)
+        return sampled_link_loss(z[self.relation[0]], z[self.relation[2]], pos, self.k, self.seed, offset,
+                                 self.objective, self.temperature, self.alpha)
 
     def metrics(self, graph, pos: Tensor = None) -> dict:
         """``link_metrics`` of the model's embeddings in eval mode, without gradients (the mode is restored)."""

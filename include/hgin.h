@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HGIN_ABI_VERSION 11
+#define HGIN_ABI_VERSION 12
 
 #define HGIN_OK 0
 #define HGIN_E_ARG (-1)        /* bad size / null pointer / unsupported combination */
@@ -464,6 +464,51 @@ int hgin_link_loss_bwd_dst_f32(const int32_t* pos_rowptr, const int32_t* pos_col
 int hgin_link_rank_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64_t seed, uint64_t offset, int64_t n_dst,
                        const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F,
                        int32_t* n_greater, int32_t* n_equal, void* stream);
+
+/* ---- A17: ranking objectives of the fused link loss (NOT IN REFERENCE; build-defined, ABI 12) -------------------
+ * hgin_link_loss_fwd_obj_f32 is hgin_link_loss_fwd_f32 with a choice of objective.  For positive e: s_0 =
+ * <z_src[s], z_dst[d]>, s_j (j = 1 .. k) the scores of its k negatives; the negatives are the draws of A13 (Philox
+ * counter offset + e k + j - 1, multiply-shift into [0, n_dst)), the scores are computed exactly as A13 computes them
+ * (same piece order, same xor-tree), and neg is bit for bit what hgin_link_loss_fwd_f32 writes.  coef has A13's layout
+ * (positives first, then negative e k + j - 1) and holds d loss / d score, so both A13 backward entry points serve
+ * every objective unchanged.
+ *
+ *   objective              | loss                                              | coef[e]                | coef[E + e k + j - 1]
+ *   -----------------------+---------------------------------------------------+------------------------+----------------------
+ *   0 HGIN_LINK_OBJ_BCE    | A13, unchanged (the call forwards to A13's launch)| unchanged              | unchanged
+ *   1 HGIN_LINK_OBJ_SOFTMAX| 1/E sum_e [ logsumexp_{t=0..k}(s_t / tau)         | (p_0 - 1) / (tau E)    | p_j / (tau E),
+ *     param = tau > 0      |             - s_0 / tau ]                         |                        | p = softmax_t(s_t / tau)
+ *   2 HGIN_LINK_OBJ_BPR    | 1/(E k) sum_e sum_j softplus(s_j - s_0)           | -sum_j sigmoid(s_j-s_0)| sigmoid(s_j - s_0)
+ *                          |                                                   |   / (E k)              |   / (E k)
+ *   3 HGIN_LINK_OBJ_SELFADV| 1/E sum_e 1/2 [ softplus(-s_0)                    | -1/2 sigmoid(-s_0) / E | 1/2 p_j sigmoid(s_j)
+ *     param = alpha >= 0   |        + sum_j p_j softplus(s_j) ],               |                        |   / E
+ *                          |   p_j = softmax_j(alpha s_j) over the k negatives,|                        |
+ *                          |   a constant (no gradient flows through p)        |                        |
+ *
+ * Softmax / logsumexp subtract the running maximum, softplus and sigmoid go through exp(-|x|): nothing overflows for
+ * finite scores of any size (selfadv: alpha s is formed in fp32, so |alpha s| must stay finite).  param is ignored by
+ * objectives 0 and 2.
+ * bpr: pair t = 0 is in the first batch, so every negative is finished as it arrives; the lanes that finish a
+ * positive's negatives keep running sums of sigmoid(s_j - s_0), joined after the last batch (lane 0 .. 3 in order)
+ * into coef[e].  softmax / selfadv need a normaliser over all of a positive's pairs and k has no bound, so they are
+ * two-phase inside the same lane group and launch: phase 1 stores each pair's raw score into its coef slot (and the
+ * drawn pair into neg) while every lane keeps an online (max, sum) of the group's scores, pairs in order t = 0 .. k
+ * (the sum leaves out the maximum's own term, so logsumexp = max + log1p(sum) resolves losses far below 1, and the
+ * softmax coefficient of the positive is formed as minus the sum of its negatives' stored coefficients, which has no
+ * cancellation near p_0 = 1 and makes a positive's stored coefficients sum to zero within rounding; so does bpr's);
+ * phase 2 walks the same pair -> lane mapping again, each lane reads back the slots it wrote itself (no fence
+ * needed), overwrites them with the coefficients and adds the pair's loss term.  The loss is summed as in A13 (lane
+ * sums, xor tree per wave, four waves in order, partials in order): run-to-run bit-identical.  Workspace, argument
+ * ranges and status codes as hgin_link_loss_fwd_f32; additionally HGIN_E_ARG for an objective outside 0 .. 3, a
+ * non-finite param, tau <= 0 or alpha < 0. */
+#define HGIN_LINK_OBJ_BCE 0
+#define HGIN_LINK_OBJ_SOFTMAX 1
+#define HGIN_LINK_OBJ_BPR 2
+#define HGIN_LINK_OBJ_SELFADV 3
+int hgin_link_loss_fwd_obj_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64_t seed, uint64_t offset,
+                               int64_t n_dst, const float* z_src, int64_t ld_src, const float* z_dst,
+                               int64_t ld_dst, int64_t F, float* coef, int64_t* neg, float* loss, void* workspace,
+                               size_t workspace_bytes, int32_t objective, float param, void* stream);
 
 /* ---- A15: full-candidate filtered ranking (NOT IN REFERENCE; build-defined, ABI 10) ----------------------------
  * For query q (s = pos[0, q], d = pos[1, q]; pos int64 [2, E] as in A13) and score(q, c) = <z_src[s], z_dst[c]>, the

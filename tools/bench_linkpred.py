@@ -11,7 +11,13 @@ path is faster by more than the spread (its slowest repeat under link_loss's fas
 its algorithmic bytes and fraction of the 8 TB/s HBM peak, and the ranking kernel.  A path that runs out of memory is
 recorded as such.  There is no CPU fallback: without a HIP device the tool prints the plan and fails.
 
+``--objective`` (include/hgin.h A17) adds the softmax / bpr / selfadv epilogues: for each one the fused forward +
+backward against ``link_loss`` with the same objective, timed like the bce pair and alternating with it in the same
+repeat loop, reported under the shape's "objectives" with the ratio to the fused bce step of the same run ("all" runs
+bce too, whose rows are produced as without the option).
+
     python tools/bench_linkpred.py --out profiles/linkpred/linkpred_bench.json
+    python tools/bench_linkpred.py --objective all --out profiles/linkpred/linkobj_bench.json
     python tools/bench_linkpred.py --configs cfg1 --scale 0.1 --k 1      # a tiny run
 """
 import argparse
@@ -27,6 +33,7 @@ for _p in (ROOT, os.path.join(ROOT, "gnn-link-prediction_amd")):
         sys.path.insert(0, _p)
 
 HBM_PEAK = 8.0e12          # bytes / s
+OBJECTIVES = ["bce", "softmax", "bpr", "selfadv"]
 DECODER_HBM_FRACTION = 0.73   # the existing dot-product decoder's recorded fraction
 
 
@@ -40,6 +47,15 @@ def fwd_algorithmic_bytes(E: int, k: int, F: int) -> int:
 
 def rank_algorithmic_bytes(E: int, k: int, F: int) -> int:
     return E * F * 4 + (1 + k) * E * F * 4 + 2 * E * 8 + 2 * E * 4
+
+
+def objectives_of(arg: str):
+    """The objectives one --objective value asks for, in the order of the C ABI's codes."""
+    if arg == "all":
+        return list(OBJECTIVES)
+    if arg not in OBJECTIVES:
+        raise SystemExit(f"--objective must be one of {', '.join(OBJECTIVES)} or all, got {arg!r}")
+    return [arg]
 
 
 def plan(configs, ks, scale: float):
@@ -82,7 +98,7 @@ def _inner_for(torch, fn, target_ms):
     return max(1, int(math.ceil(target_ms / max(t, 1e-3))))
 
 
-def run_shape(torch, shape, repeats, warmup, target_ms, seed=1234):
+def run_shape(torch, shape, repeats, warmup, target_ms, seed=1234, objectives=("bce",)):
     from hgin.linkpred import link_loss, link_ranks, sampled_link_loss
     dev = "cuda"
     n_src, n_dst, E, F, k = (shape[x] for x in ("n_src", "n_dst", "E", "F", "k"))
@@ -92,10 +108,13 @@ def run_shape(torch, shape, repeats, warmup, target_ms, seed=1234):
     z_src = (torch.randn(n_src, F, generator=g, device=dev) * 0.1).requires_grad_(True)
     z_dst = (torch.randn(n_dst, F, generator=g, device=dev) * 0.1).requires_grad_(True)
 
-    def step_of(loss_fn):
+    def step_of(loss_fn, objective):
+        # bce goes through the call without the argument, as every caller before the objectives existed
+        kw = {} if objective == "bce" else {"objective": objective}
+
         def fn(step):
             z_src.grad = z_dst.grad = None
-            loss_fn(z_src, z_dst, pos, k, seed, step * E * k).backward()
+            loss_fn(z_src, z_dst, pos, k, seed, step * E * k, **kw).backward()
         return fn
 
     def fwd_only(step):
@@ -105,45 +124,63 @@ def run_shape(torch, shape, repeats, warmup, target_ms, seed=1234):
     def rank_only(step):
         link_ranks(z_src, z_dst, pos, k, seed, step * E * k)
 
-    fused, base = step_of(sampled_link_loss), step_of(link_loss)
+    fused = {o: step_of(sampled_link_loss, o) for o in objectives}
+    base = {o: step_of(link_loss, o) for o in objectives}
     out = dict(shape)
     base_ok = True
     try:
         for s in range(warmup):
-            fused(s)
-            base(s)
+            for o in objectives:
+                fused[o](s)
+                base[o](s)
         torch.cuda.synchronize()
     except torch.OutOfMemoryError:
         base_ok = False
         z_src.grad = z_dst.grad = None
         torch.cuda.empty_cache()
         for s in range(warmup):
-            fused(s)
+            for o in objectives:
+                fused[o](s)
         torch.cuda.synchronize()
-    inner_f = _inner_for(torch, fused, target_ms)
-    inner_b = _inner_for(torch, base, target_ms) if base_ok else 0
-    t_f, t_b, step = [], [], warmup
-    for _ in range(repeats):      # the two paths alternate
-        t_f.append(_timed(torch, fused, inner_f, step))
+    inner_f = {o: _inner_for(torch, fused[o], target_ms) for o in objectives}
+    inner_b = {o: _inner_for(torch, base[o], target_ms) if base_ok else 0 for o in objectives}
+    t_f, t_b, step = {o: [] for o in objectives}, {o: [] for o in objectives}, warmup
+    for _ in range(repeats):      # every path of every objective alternates
+        for o in objectives:
+            t_f[o].append(_timed(torch, fused[o], inner_f[o], step))
+            if base_ok:
+                t_b[o].append(_timed(torch, base[o], inner_b[o], step))
+        step += max(max(inner_f.values()), max(inner_b.values()))
+
+    def pair(o):
+        res = {"fused": dict(_stats(t_f[o]), inner=inner_f[o])}
         if base_ok:
-            t_b.append(_timed(torch, base, inner_b, step))
-        step += max(inner_f, inner_b)
-    out["fused"] = dict(_stats(t_f), inner=inner_f)
-    if base_ok:
-        out["link_loss"] = dict(_stats(t_b), inner=inner_b)
-        out["link_loss_over_fused"] = out["link_loss"]["median_ms"] / out["fused"]["median_ms"]
-        out["fused_faster_beyond_spread"] = out["fused"]["max_ms"] < out["link_loss"]["min_ms"]
-    else:
-        out["link_loss"] = {"error": "out of memory"}
+            res["link_loss"] = dict(_stats(t_b[o]), inner=inner_b[o])
+            res["link_loss_over_fused"] = res["link_loss"]["median_ms"] / res["fused"]["median_ms"]
+            res["fused_faster_beyond_spread"] = res["fused"]["max_ms"] < res["link_loss"]["min_ms"]
+        else:
+            res["link_loss"] = {"error": "out of memory"}
+        return res
+
+    if "bce" in objectives:
+        out.update(pair("bce"))
+    others = [o for o in objectives if o != "bce"]
+    if others:
+        out["objectives"] = {o: pair(o) for o in others}
+        if "bce" in objectives:   # the same run, the same box: the epilogue's cost over the bce step
+            for o in others:
+                out["objectives"][o]["fused_over_fused_bce"] = (out["objectives"][o]["fused"]["median_ms"]
+                                                               / out["fused"]["median_ms"])
     z_src.grad = z_dst.grad = None
-    for name, fn, nbytes in (("fused_forward", fwd_only, shape["fwd_algorithmic_bytes"]),
-                             ("rank", rank_only, shape["rank_algorithmic_bytes"])):
-        inner = _inner_for(torch, fn, target_ms)
-        st = _stats([_timed(torch, fn, inner, warmup + r * inner) for r in range(repeats)])
-        st.update(inner=inner, algorithmic_bytes=nbytes,
-                  hbm_fraction=nbytes / (st["median_ms"] * 1e-3) / HBM_PEAK)
-        out[name] = st
-    out["decoder_hbm_fraction_recorded"] = DECODER_HBM_FRACTION
+    if "bce" in objectives:
+        for name, fn, nbytes in (("fused_forward", fwd_only, shape["fwd_algorithmic_bytes"]),
+                                 ("rank", rank_only, shape["rank_algorithmic_bytes"])):
+            inner = _inner_for(torch, fn, target_ms)
+            st = _stats([_timed(torch, fn, inner, warmup + r * inner) for r in range(repeats)])
+            st.update(inner=inner, algorithmic_bytes=nbytes,
+                      hbm_fraction=nbytes / (st["median_ms"] * 1e-3) / HBM_PEAK)
+            out[name] = st
+        out["decoder_hbm_fraction_recorded"] = DECODER_HBM_FRACTION
     del z_src, z_dst, pos
     torch.cuda.empty_cache()
     return out
@@ -157,10 +194,12 @@ def main(argv=None) -> int:
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--target-ms", type=float, default=30.0, help="device time of one timed repeat, at least")
+    ap.add_argument("--objective", default="bce", help="bce, softmax, bpr, selfadv or all (include/hgin.h A17)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     if args.repeats < 5:
         ap.error("--repeats must be at least 5")
+    objectives = objectives_of(args.objective)
     shapes = plan(args.configs.split(","), [int(v) for v in args.k.split(",")], args.scale)
     for s in shapes:
         print("plan:", json.dumps(s), file=sys.stderr)
@@ -171,11 +210,12 @@ def main(argv=None) -> int:
         return 2
     from hgin import _lib
     _lib.lib()
-    results = [run_shape(torch, s, args.repeats, args.warmup, args.target_ms) for s in shapes]
-    both = [r for r in results if "error" not in r["link_loss"]]
+    results = [run_shape(torch, s, args.repeats, args.warmup, args.target_ms, objectives=objectives) for s in shapes]
+    pairs = [r for r in results if "link_loss" in r] + [p for r in results for p in r.get("objectives", {}).values()]
+    both = [p for p in pairs if "error" not in p["link_loss"]]
     doc = {"tool": "tools/bench_linkpred.py", "device": torch.cuda.get_device_name(0), "hbm_peak_bytes_per_s": HBM_PEAK,
-           "repeats": args.repeats, "warmup": args.warmup, "shapes": results,
-           "fused_faster_at_every_shape_both_ran": all(r["fused_faster_beyond_spread"] for r in both)}
+           "repeats": args.repeats, "warmup": args.warmup, "objectives": objectives, "shapes": results,
+           "fused_faster_at_every_shape_both_ran": all(p["fused_faster_beyond_spread"] for p in both)}
     text = json.dumps(doc)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
