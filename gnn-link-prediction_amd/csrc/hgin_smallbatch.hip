@@ -913,6 +913,27 @@ __global__ __launch_bounds__(kSbThreads) void k_sb_readout(SbArgs a) {
 constexpr int kSbRowsM = 32;
 constexpr int kRoThreadsM = 512;   // 8 waves: 2 per SIMD, so one wave's LDS / MFMA latency overlaps the other's
 
+// k_sb_readout_mfma's tile LDS floats without the staged parameters, for tiles of R rows: in0 [R][w0 | 1] | z_i, y_i
+// [R][rw_i | 1] per hidden layer | gbuf x2 [R][maxw | 1] | outv [R] | red
+__host__ __device__ __forceinline__ int64_t ro_mfma_floats(int64_t w0, int nhid, const int* rw, int R) {
+  int64_t act = w0 | 1, maxw = w0;
+  for (int i = 0; i < nhid; ++i) {
+    act += 2 * (rw[i] | 1);
+    maxw = rw[i] > maxw ? rw[i] : maxw;
+  }
+  return R * (act + 2 * (maxw | 1)) + R + (kRoThreadsM / 64) * 32 * 33;
+}
+// The tile rows of the MFMA readout.  Mode 4 (the weights through the caches) halves its tiles to 16 rows where the
+// 32-row tile's activations alone exceed the 159 KiB hgin/smallbatch.py grants a readout (two 256-wide layers: 232,704
+// B against 133,248 B): the MFMA's rows past 16 are zeros (tile_mfma's nr), every output is the same sum in the same
+// order, and the tile partials of the loss and the slope are twice as many.  Every other mode and shape: 32 rows.
+constexpr int kSbRowsMH = 16;
+constexpr int64_t kRoLdsGrant = 159 * 1024;
+__host__ __device__ __forceinline__ int ro_rows_m(int mode, int64_t w0, int nhid, const int* rw) {
+  if (mode != 4) return kSbRowsM;
+  return 4 * ro_mfma_floats(w0, nhid, rw, kSbRowsM) > kRoLdsGrant ? kSbRowsMH : kSbRowsM;
+}
+
 // C[32 x N] = A[32 x K] B[K x N] for one tile: A(r, k) = A[r asr + k ask] (rows >= nr read as zero), B(k, n) =
 // Bm[k bsk + n bsn].  The ceil(N / 32) column blocks go to the NT / 64 waves; with fewer blocks than waves a block's
 // k-steps are split over the idle ones (a fixed power-of-two split) and the partials, parked in red [NT / 64][32][33],
@@ -991,7 +1012,7 @@ __device__ __forceinline__ void tile_mfma(const float* A, int lda, int nr, const
 
 // kWL false (hgin_sb_readout_lds_bytes mode 4: the staged weights would not fit, e.g. hidden 128): the MFMA operands'
 // W rows and the head's W are read through the caches instead
-template <bool kWL>
+template <bool kWL, int R = kSbRowsM>
 __global__ __launch_bounds__(kRoThreadsM) void k_sb_readout_mfma(SbArgs a) {
   extern __shared__ float sm[];
   constexpr int NT = kRoThreadsM;
@@ -999,7 +1020,6 @@ __global__ __launch_bounds__(kRoThreadsM) void k_sb_readout_mfma(SbArgs a) {
   const int tid = threadIdx.x;
   const int H = a.H;
   const int m = a.m_valid[0];
-  constexpr int R = kSbRowsM;
   const int ntile = (m + R - 1) / R;
   const int tile = blockIdx.x;
   if (tile >= ntile) return;   // (the grid is sized for the capacity; uniform per workgroup)
@@ -1708,8 +1728,12 @@ __global__ __launch_bounds__(kSbThreads, kM ? 1 : 4) void k_sb_bwd_w(SbArgs a, i
       __syncthreads();
       if (tid < H)   // the bias partial: the rows in order
         for (int rr = 0; rr < nr; ++rr) bsum = __fadd_rn(bsum, s_g[rr * lg + tid]);
+      // (each tile_mfma call below parks its k-split partials in redm when K <= 64 and sums them after its own barrier:
+      // the barrier ahead of every call but the first keeps a wave that is done from overwriting partials another
+      // wave of the previous call is still summing)
       for (int sb = 0; sb < nr; sb += 32) {   // g_comb rows (row-local: k_sb_bwd_in reads them after this launch)
         const int ns = nr - sb < 32 ? nr - sb : 32;
+        if (sb) __syncthreads();
         tile_mfma<kSbThreads, 16>(s_g + sb * lg, lg, ns, cv.w, K, 1, K, H, redm, [&](int r, int k, float v) {
           const int i = rb + sb + r;
           gc[(int64_t)i * a.kmax + k] = v;
@@ -1722,6 +1746,7 @@ __global__ __launch_bounds__(kSbThreads, kM ? 1 : 4) void k_sb_bwd_w(SbArgs a, i
       }
       for (int h0 = 0; h0 < H; h0 += 32) {   // W partial [h][k] += sum over the staged rows of g_z[h] comb[k]
         const int nh = H - h0 < 32 ? H - h0 : 32;
+        __syncthreads();
         tile_mfma_s<kSbThreads>(s_g + h0, 1, lg, nh, s_in, lk, 1, K, nr, redm, [&](int r, int k, float v) {
           float* e = part + (int64_t)(h0 + r) * K + k;
           *e = rb == i0 ? v : __fadd_rn(*e, v);
@@ -1859,7 +1884,9 @@ __global__ __launch_bounds__(kSbThreads) void k_sb_final(SbArgs a) {
     ad.bc2_sqrt = sqrtf(__fsub_rn(1.0f, powf(a.beta2, st)));
   }
   const int m = a.m_valid[0];
-  const int rows = a.ro_wlds >= 2 ? kSbRowsM : kSbRows;   // the readout tiles' rows (one loss / slope partial each)
+  // the readout tiles' rows (one loss / slope partial each)
+  const int rows = a.ro_wlds >= 2 ? ro_rows_m(a.ro_wlds, a.H + (a.concat_path ? a.fdim[0] : 0) + a.pool_w, a.nhid, a.rw)
+                                  : kSbRows;
   const int ntile = (m + rows - 1) / rows;
   float lp = 0.0f, sp = 0.0f;
   for (int t = tid; t < ntile; t += kSbThreads) {
@@ -2274,10 +2301,9 @@ extern "C" int hgin_sb_readout_lds_bytes(int64_t H, int64_t f_path, int concat_p
     return HGIN_OK;
   }
   if (with_weights == 2 || with_weights == 4) {   // k_sb_readout_mfma: 32-row tiles, odd row strides, the split
-    int64_t act = w0 | 1;                            // partials (4: the weights through the caches)
-    for (int i = 0; i < nhid; ++i) act += 2 * (widths[i] | 1);
-    *bytes = sizeof(float) * (size_t)((with_weights == 2 ? wts : 0) + kSbRowsM * (act + 2 * (maxw | 1)) + kSbRowsM +
-                                      (kRoThreadsM / 64) * 32 * 33);
+    // partials (4: the weights through the caches, and 16-row tiles where 32 rows exceed the grant: ro_rows_m)
+    const int R = ro_rows_m(with_weights, w0, nhid, widths);
+    *bytes = sizeof(float) * (size_t)((with_weights == 2 ? wts : 0) + ro_mfma_floats(w0, nhid, widths, R));
     return HGIN_OK;
   }
   *bytes = sizeof(float) * (size_t)(kSbRows * (tot + 2 * maxw) + kSbRows + (with_weights ? wts : 0));
@@ -2311,6 +2337,7 @@ extern "C" int hgin_sb_step(const void* args, size_t args_bytes, size_t readout_
                            reinterpret_cast<const void*>(k_sb_readout<false>),
                            reinterpret_cast<const void*>(k_sb_readout_mfma<true>),
                            reinterpret_cast<const void*>(k_sb_readout_mfma<false>),
+                           reinterpret_cast<const void*>(k_sb_readout_mfma<false, kSbRowsMH>),
                            reinterpret_cast<const void*>(k_sb_bn_fwd), reinterpret_cast<const void*>(k_sb_bn_head),
                            reinterpret_cast<const void*>(k_sb_bn_bwd)}) {
       hipFuncAttributes fa;
@@ -2386,11 +2413,17 @@ extern "C" int hgin_sb_step(const void* args, size_t args_bytes, size_t readout_
       k_sb_bn_bwd<<<nt, kRoThreadsM, lb, s>>>(a, i);
     }
   } else if (a.ro_wlds == 2 || a.ro_wlds == 4) {
-    const unsigned g = (unsigned)ceil_div((int64_t)a.n_tiles * kSbRows, (int64_t)kSbRowsM);
+    const int rows = ro_rows_m(a.ro_wlds, a.H + (a.concat_path ? a.fdim[0] : 0) + a.pool_w, a.nhid, a.rw);
+    const unsigned g = (unsigned)ceil_div((int64_t)a.n_tiles * kSbRows, (int64_t)rows);
+    HGIN_ARG_CHECK(readout_lds >= sizeof(float) * (size_t)ro_mfma_floats(a.H + (a.concat_path ? a.fdim[0] : 0) + a.pool_w,
+                                                                         a.nhid, a.rw, rows),
+                   "hgin_sb_step: readout LDS %zu below the %d-row tile's", readout_lds, rows);
     if (a.ro_wlds == 2)
       k_sb_readout_mfma<true><<<g, kRoThreadsM, readout_lds, s>>>(a);
-    else
+    else if (rows == kSbRowsM)
       k_sb_readout_mfma<false><<<g, kRoThreadsM, readout_lds, s>>>(a);
+    else
+      k_sb_readout_mfma<false, kSbRowsMH><<<g, kRoThreadsM, readout_lds, s>>>(a);
   }
   else if (a.ro_wlds)
     k_sb_readout<true><<<a.n_tiles, kSbThreads, readout_lds, s>>>(a);

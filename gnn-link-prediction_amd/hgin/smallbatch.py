@@ -487,7 +487,8 @@ class SmallBatchStep:
         widths = (ctypes.c_int32 * MAX_HID)(*[a.rw[i] for i in range(MAX_HID)])
         lds = ctypes.c_size_t(0)
         # the readout: 32-row tiles on the matrix cores, their weights in LDS where they fit, else read through the
-        # caches (mode 4); the 8-row scalar tiles (with the hidden weights in LDS, 1, else without, 0) where neither fits
+        # caches (mode 4; on 16-row tiles where 32 rows of the widest layers exceed the LDS: the library's ro_rows_m,
+        # folded into hgin_sb_readout_lds_bytes); the 8-row scalar tiles (with the hidden weights in LDS, 1, else without, 0) where neither fits
         # the LDS, or asked for (readout="scalar")
         # (MLP_BN: the k_sb_bn_* launches, mode 3)
         # (MLP_BN in evaluation: the plain readout with BatchNorm's running-statistics affine map, bn_eval)

@@ -17,6 +17,8 @@ from hgin import HetroGIN
 from hgin.data import CONFIGS, scaled_config, synthetic_graph
 from hgin.store import GraphStore
 
+import smallbatch_cases as sc
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
@@ -48,23 +50,11 @@ def _oracle_twin(model, cfg, layers=None):
     return ref
 
 
-def _g(p):
-    """A fused-step parameter's gradient; the dead convs' parameters keep .grad None, as in the reference."""
-    return p.grad.detach() if p.grad is not None else torch.zeros_like(p.detach())
-
-
-def _host_batch(store, ids):
-    """The batch on the host, pinned to the numpy restatement of PyG's collation of the same graphs."""
-    from oracle import collate_np
-    b = store.collate(ids).to("cpu")
-    want = collate_np.collate([collate_np.from_graph(store.collate([i]).to("cpu")) for i in ids])
-    for t in b.x:
-        assert torch.equal(b.x[t], torch.from_numpy(want["x"][t])), t
-        assert torch.equal(b.batch[t], torch.from_numpy(want["batch"][t])), t
-    for r in b.edge_index:
-        assert torch.equal(b.edge_index[r], torch.from_numpy(want["edge_index"][r])), r
-    assert torch.equal(b.y, torch.from_numpy(want["y"]))
-    return b
+# shared with tests/test_gpu_smallbatch_edges.py (tests/smallbatch_cases.py): a fused-step parameter's gradient (the dead
+# convs' parameters keep .grad None, as in the reference); the batch on the host, pinned to the numpy restatement of
+# PyG's collation of the same graphs (x, batch vectors, edge_index, y, bit for bit)
+_g = sc.grad_of
+_host_batch = sc.host_batch
 
 
 @pytest.mark.parametrize("readout", ["mfma", "scalar"])
@@ -73,7 +63,6 @@ def test_fused_step_vs_oracle(layers, readout, monkeypatch):
     """One fused step (Adam at lr 0) against the CPU oracle's forward / sqrt-MAPE backward on the host-collated batch;
     the readout on the 32-row MFMA tiles (default) and on the 8-row scalar tiles (readout="scalar")."""
     from hgin.smallbatch import SmallBatchStep
-    from oracle.pyg_cpu import mape
     store, cfg = _store(10, seed=11)
     ids = [2, 8, 5, 0]
     m1 = _model(cfg, layers)
@@ -85,16 +74,9 @@ def test_fused_step_vs_oracle(layers, readout, monkeypatch):
     lv = float(step.step(ids))
     torch.cuda.synchronize()
     b = _host_batch(store, ids)
-    out = ref(b.x_dict(), b.edge_index_dict(), b.batch["path"])
-    lv_ref = mape(out, b.y.reshape(-1, 1))
-    torch.sqrt(lv_ref).backward()
-    assert abs(lv - float(lv_ref)) <= 1e-5 * abs(float(lv_ref)), (lv, float(lv_ref))
-    for (n, p), (n2, q) in zip(m1.named_parameters(), ref.named_parameters()):
-        assert n == n2
-        assert (p.grad is None) == (q.grad is None), n   # the dead convs' parameters: no gradient on either side
-        want = q.grad if q.grad is not None else torch.zeros_like(q)
-        d = float((_g(p).cpu() - want).double().norm())
-        assert d <= 1e-4 * float(want.double().norm()) + 1e-9, (n, d, float(want.norm()))
+    # (the shared check: loss 1e-5 relative; per parameter .grad None on both sides or neither — the dead convs — and
+    # within 1e-4 of the oracle's norm + 1e-9; the oracle in fp32, as before)
+    sc.check_step(m1, ref, lv, sc.oracle_step(ref, b), tag=(layers, readout))
 
 
 @pytest.mark.parametrize("variant", ["hidden128", "hidden64", "hidden96_L3", "global_feats", "global_feats_no_concat",
