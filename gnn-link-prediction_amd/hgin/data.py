@@ -25,6 +25,8 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
+from . import ops
+
 EdgeType = Tuple[str, str, str]
 
 REL_PL: EdgeType = ("path", "uses", "link")
@@ -130,9 +132,28 @@ class HeteroGraph:
     y: torch.Tensor
     batch: Dict[str, torch.Tensor]
 
+    # Whether the feature tensors are data that stay the same from step to step (a resident graph), so that the first
+    # layer's aggregate of them may be computed once and reused (ops.STATIC_AGG).  A class attribute, not a field
+    # (subclasses are constructed positionally).  The contract is the CSR cache's: an edit through torch bumps the
+    # tensor's _version and invalidates the cached aggregate; an edit through raw device pointers must be followed by
+    # features_changed().  Containers whose buffers are refilled in place (store.PaddedBatch) turn it off.
+    static_features = True
+
     def x_dict(self) -> Dict[str, torch.Tensor]:
         # A fresh dict per call, like HeteroData.x_dict: HetroGIN.forward assigns into it (models.py:333-342).
+        for t in self.x.values():
+            if self.static_features:
+                ops.mark_static(t)
+            else:
+                ops.unmark_static(t)
         return dict(self.x)
+
+    def features_changed(self) -> None:
+        """Call after writing the feature tensors through anything torch does not see (raw device pointers, a
+        kernel of your own): drops the cached first-layer aggregates and bumps the tensors' versions."""
+        for t in self.x.values():
+            ops.drop_static_cache(t)
+            torch.autograd.graph.increment_version(t)
 
     def edge_index_dict(self) -> Dict[EdgeType, torch.Tensor]:
         return dict(self.edge_index)

@@ -125,8 +125,15 @@ class CapturedStaticStep:
             for _ in range(max(int(warmup), 1)):
                 train_step(model, opt, graph, reducer=reducer)
         torch.cuda.current_stream().wait_stream(side)
+        self.fwd_bwd = self.opt_graph = None
+        self._capture()
+
+    def _capture(self) -> None:
+        model, opt, graph, reducer = self.model, self.opt, self.graph, self.reducer
+        self.fwd_bwd = self.opt_graph = self.loss = None    # a re-capture frees the old graphs' pool first
         torch.cuda.synchronize()
         opt.zero_grad(set_to_none=True)
+        self._features = self._feature_state()
         self.fwd_bwd = torch.cuda.CUDAGraph()
         self.opt_graph: Optional[torch.cuda.CUDAGraph] = None
         with torch.cuda.graph(self.fwd_bwd):
@@ -138,8 +145,19 @@ class CapturedStaticStep:
             with torch.cuda.graph(self.opt_graph, pool=self.fwd_bwd.pool()):
                 opt.step()
 
+    def _feature_state(self):
+        """The warm-up left the first layer's aggregate of the features in ops' static cache and the capture holds its
+        pointer instead of the launches, so a replay no longer follows an edit of the features: their versions
+        (bumped by in-place torch edits and by ``graph.features_changed()``) are checked on every step."""
+        x = getattr(self.graph, "x", None)
+        return tuple(t._version for t in x.values()) if isinstance(x, dict) else ()
+
     def step(self) -> torch.Tensor:
-        """One training step; returns the device loss_value (no host sync)."""
+        """One training step; returns the device loss_value (no host sync).  If the graph's features were edited
+        since the capture, the step is captured again first (that capture aggregates them itself: correct, and the
+        four launches slower until a new CapturedStaticStep is built)."""
+        if self._feature_state() != self._features:
+            self._capture()
         self.fwd_bwd.replay()
         if self.opt_graph is None:
             return self.loss

@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import weakref
 from dataclasses import dataclass
 from typing import Optional
 
@@ -550,6 +551,133 @@ def _zero(device) -> Tensor:
 LAZY_SELF = True     # tests compare the lazy self-term gradient with the materialised one (bit-identical)
 
 
+def _switch(value: Optional[str], default: bool = True) -> bool:
+    """An on / off environment value: unset or empty -> ``default``; 0 / off / false / no -> off; anything else on."""
+    if value is None or not value.strip():
+        return default
+    return value.strip().lower() not in ("0", "off", "false", "no")
+
+
+# ---------------------------------------------------------------------------------------------------
+# static data inputs: the first layer's aggregate, once per graph instead of once per step
+# ---------------------------------------------------------------------------------------------------
+# The first HeteroConv layer aggregates the raw node features (_gin_forward, COMBINE_CONCAT with data inputs: comb =
+# sum of x_src over the CSR, COMBINE_NONE).  Features of a resident graph carry no gradient and, like its edge lists,
+# do not change from step to step, so that aggregate is the same values every step: it is computed once and kept on
+# the feature tensor object (the way the CSR / CSC live on edge_index), and later steps skip the launch.
+#   * Eligible: a tensor marked static (mark_static; HeteroGraph.x_dict() marks what it hands out, PaddedBatch.x_dict()
+#     — buffers refilled through raw pointers inside captured replays — flags its tensors volatile), requires_grad
+#     False, no grad_fn.  A tensor made inside the model (a slice, a cat, an activation) is a new object: never marked.
+#   * Valid while the RelationGraph object (replaced when edge_index._version moves) and the tensor's _version,
+#     data_ptr(), shape, strides and dtype are what they were at the fill.  In-place edits through torch bump _version;
+#     edits through raw device pointers must be followed by HeteroGraph.features_changed().
+#   * Stream capture: no entry is stored while the current stream is capturing (a tensor of a graph's private pool must
+#     not outlive it, and a captured fill would re-run on every replay anyway); a lookup during capture is served, and a
+#     miss then computes inside the capture as before.  torch.cuda.graph synchronises the device before it begins to
+#     capture, so an entry stored earlier is complete; a captured step has the cached pointer baked in, so it must be
+#     re-captured after the features change (CapturedStaticStep does).
+#   * Streams: an event is recorded after the fill; a hit from another stream (outside capture) waits on it and
+#     record_stream()s the cached tensor.
+#   * Read-only: every consumer of the layer-0 comb takes it as a pure input — the weight-stationary fp32 forward
+#     (k_wss_f32, both passes), the tiled K = 512 forward, hgin_gin_mlp_bwd_w_* (b1 = comb, b2 = x_dst), the bf16
+#     forms (k_ws_bf16 / k_gemm_nt_bf16, the zy forward and its dW) — all const __restrict__ A / B operands; nothing in
+#     this module writes comb after aggregate_into.  The result is the same kernel's output, reused: bit-identical.
+# Not covered: the dst-range partition's per-step all-gather of raw features, the GAT path, _AggregateFn with a user nn.
+# HGIN_STATIC_AGG=0 aggregates every step (the on / off tests and measurements).
+STATIC_AGG = _switch(os.environ.get("HGIN_STATIC_AGG"))
+_STATIC_FLAG, _STATIC_CACHE = "_hgin_static", "_hgin_static_agg"
+
+
+def mark_static(t: Tensor, force: bool = False) -> bool:
+    """Declare ``t`` data that stays the same from step to step (see STATIC_AGG).  A tensor flagged volatile
+    (unmark_static) stays so unless ``force``.  Returns whether ``t`` is now marked."""
+    if getattr(t, _STATIC_FLAG, None) is False and not force:
+        return False
+    setattr(t, _STATIC_FLAG, True)
+    return True
+
+
+def unmark_static(t: Tensor) -> None:
+    """Flag ``t`` volatile — its storage is rewritten behind torch's back (refilled batch buffers): its entries are
+    freed and it is never served from the cache until mark_static(t, force=True)."""
+    setattr(t, _STATIC_FLAG, False)
+    drop_static_cache(t)
+
+
+def is_static(t: Tensor) -> bool:
+    return getattr(t, _STATIC_FLAG, None) is True
+
+
+def drop_static_cache(t: Tensor) -> None:
+    """Free the cached aggregates of ``t`` (the mark stays)."""
+    if getattr(t, _STATIC_CACHE, None) is not None:
+        delattr(t, _STATIC_CACHE)
+
+
+def static_key(t: Tensor) -> tuple:
+    """What must be unchanged on the feature tensor for a cached aggregate of it to be valid."""
+    return (t._version, t.data_ptr(), tuple(t.shape), tuple(t.stride()), t.dtype)
+
+
+def static_cache(t: Tensor) -> list:
+    """[(RelationGraph, cached aggregate)] of the live entries on ``t`` (tests, diagnostics)."""
+    out = []
+    for e in (getattr(t, _STATIC_CACHE, None) or {}).values():
+        g = e.graph()
+        if g is not None:
+            out.append((g, e.out))
+    return out
+
+
+class _StaticAgg:
+    __slots__ = ("key", "graph", "out", "event", "stream")
+
+    def __init__(self, key, graph, out, event, stream):
+        self.key, self.graph, self.out, self.event, self.stream = key, weakref.ref(graph), out, event, stream
+
+
+def _graph_current(g: "RelationGraph") -> bool:
+    c = getattr(g.edge_index, "_hgin_graphs", None)
+    return c is not None and c[0] == g.edge_index._version and any(v is g for v in c[1].values())
+
+
+def _data_aggregate(graph: "RelationGraph", x_src: Tensor) -> Tensor:
+    """comb = sum of x_src over graph.csr (COMBINE_NONE) for a layer whose inputs are data: served from the cache on
+    ``x_src`` when it is eligible and the entry valid (STATIC_AGG above), computed — and stored, outside capture —
+    otherwise.  The caller must not write the result."""
+    eligible = STATIC_AGG and is_static(x_src) and not x_src.requires_grad and x_src.grad_fn is None
+    e = key = None
+    if eligible:
+        key = static_key(x_src)
+        e = (getattr(x_src, _STATIC_CACHE, None) or {}).get(id(graph))
+        if e is not None and not (e.key == key and e.graph() is graph):
+            del getattr(x_src, _STATIC_CACHE)[id(graph)]      # stale: free it now, whether or not a new one is stored
+            e = None
+    if e is not None:
+        assert getattr(x_src, _STATIC_FLAG, None) is not False, "a volatile tensor was served from the static cache"
+        cur = torch.cuda.current_stream(x_src.device)
+        if cur != e.stream and not torch.cuda.is_current_stream_capturing():
+            cur.wait_event(e.event)
+            e.out.record_stream(cur)
+        return e.out
+    comb = torch.empty(graph.n_dst, x_src.size(1), dtype=x_src.dtype, device=x_src.device)
+    aggregate_into(graph.csr, x_src, None, None, COMBINE_NONE, comb)
+    if not eligible or torch.cuda.is_current_stream_capturing():
+        return comb
+    cur = torch.cuda.current_stream(x_src.device)
+    event = torch.cuda.Event()
+    event.record(cur)
+    # entries of graphs that are gone or were replaced (an edited edge_index) go with this store
+    entries = {k: v for k, v in (getattr(x_src, _STATIC_CACHE, None) or {}).items()
+               if v.graph() is not None and _graph_current(v.graph())}
+    entries[id(graph)] = _StaticAgg(key, graph, comb, event, cur)
+    try:
+        setattr(x_src, _STATIC_CACHE, entries)
+    except (AttributeError, RuntimeError):
+        pass
+    return comb
+
+
 class _LazySelf:
     """A node type's running gradient that is still only (1 + eps) C: the first self-term contribution of an ADD-mode
     GINConv (C = its g_comb), kept unmaterialised when the next use is a CSC aggregate's running gradient, which then
@@ -614,9 +742,9 @@ def _gin_forward(x_src, x_dst, eps, weight, bias, prelu, accum, graph: RelationG
     if mode == COMBINE_CONCAT and data_inputs:
         # inputs are data (the first layer): the backward never needs the concat, so the self half
         # (1 + eps) x_dst is formed in the GEMM's tile loads instead of being written by the aggregate and
-        # read back (2 * N_dst * F_dst * s bytes less per relation); comb holds the aggregate only
-        comb = torch.empty(graph.n_dst, f_src, dtype=x_src.dtype, device=x_src.device)
-        aggregate_into(graph.csr, x_src, None, None, COMBINE_NONE, comb)
+        # read back (2 * N_dst * F_dst * s bytes less per relation); comb holds the aggregate only — the same values
+        # every step when x_src is a resident graph's features, so it may be the cached tensor (read-only from here)
+        comb = _data_aggregate(graph, x_src)
         if x_src.dtype == torch.bfloat16 and eps is not None and weight.dtype == torch.float32:
             # bf16 storage: (1 + eps) is folded into the self half of the weight operand, [W_agg | (1 + eps) W_self]
             # rounded to bf16 once from the fp32 master, instead of bf16((1 + eps) x_dst) on every row — the same

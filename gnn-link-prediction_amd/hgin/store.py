@@ -489,7 +489,12 @@ class _DescPlan:
 @dataclass
 class PaddedBatch(HeteroGraph):
     """Static-capacity batch buffers (GraphStore.padded_batch): rows past the current batch are isolated
-    padding vertices; ``m_valid`` (device int32) holds the current batch's path count for the fused loss."""
+    padding vertices; ``m_valid`` (device int32) holds the current batch's path count for the fused loss.
+
+    Never static: ``collate_into`` rewrites the feature buffers with hgin_batched_copy through raw pointers, inside
+    captured replays, where no version moves — a cached first-layer aggregate (ops.STATIC_AGG) would be stale, so
+    ``x_dict()`` flags the tensors volatile on every call."""
+    static_features = False
     m_valid: Tensor = None
     csr: Dict[EdgeType, ops.Csr] = None
     csc: Dict[EdgeType, ops.Csr] = None

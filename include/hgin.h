@@ -85,7 +85,11 @@ int hgin_csr_build(const int64_t* edge_index, int64_t n_edges, int key_row, int6
  * eps: device float[1] (the GINConv eps Parameter, models.py:191-194).  Rows with no edges get 0.
  * out must not overlap x_src or x_dst (the kernels read them through restrict-qualified pointers); the
  * backward's running-gradient accumulation (ADD, eps 0) writes a fresh buffer for that reason.
- * Bit-exact against CPU scatter_add_ + cat / add on the same inputs. */
+ * Bit-exact against CPU scatter_add_ + cat / add on the same inputs.
+ * The Python layer may skip this launch: the NONE-mode aggregate of a layer's data inputs (a resident graph's
+ * features: no gradient, unchanged between steps) is computed once per (feature tensor, graph) and its output
+ * reused read-only by the GEMMs that follow (hgin/ops.py STATIC_AGG).  The entry point and the ABI are unchanged;
+ * a caller of the C interface that wants the same saving keeps the output and passes it on itself. */
 int hgin_aggregate_f32(const int32_t* rowptr, const int32_t* col, int64_t n_rows,
                        const float* x_src, int64_t ld_src, int64_t f_src,
                        const float* x_dst, int64_t ld_dst, int64_t f_dst,
