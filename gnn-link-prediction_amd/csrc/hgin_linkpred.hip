@@ -196,13 +196,19 @@ __device__ __forceinline__ float soft_arg(float s, float scale) {
 
 // Weights by objective (launch_link_fwd): bce w_pos = 0.5 / E, w_neg = 0.5 / (E k); softmax w_pos = 1 / E (loss),
 // w_neg = 1 / (tau E) (coefficients), xscale = 1 / tau; bpr w_neg = 1 / (E k); selfadv w_pos = 0.5 / E, xscale = alpha.
-template <int VEC, int G, bool ONE, bool RANK, int OBJ>
+//
+// A18 (GIVEN): positive e has K = k + m negatives: pairs t = 1 .. k are the draws above (uniform count k, which may
+// be 0: then no Philox block is computed), pairs t = k + 1 .. k + m take destination given[e * m + (t - k - 1)].
+// K takes k's place everywhere else (slots, neg, normalisers, ranks); a batch that straddles the boundary clips its
+// Philox window to its drawn pairs.  Without GIVEN, K = k and given / m are not read.
+template <int VEC, int G, bool ONE, bool RANK, int OBJ, bool GIVEN>
 __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ pos, int64_t E, int k, uint64_t seed,
                                                   uint64_t offset, uint32_t n_dst, const float* __restrict__ zs,
                                                   int64_t lds, const float* __restrict__ zd, int64_t ldd, int F,
                                                   float w_pos, float w_neg, float xscale, float* __restrict__ coef,
                                                   int64_t* __restrict__ neg, float* __restrict__ partial,
-                                                  int32_t* __restrict__ n_gt, int32_t* __restrict__ n_eq) {
+                                                  int32_t* __restrict__ n_gt, int32_t* __restrict__ n_eq,
+                                                  const int32_t* __restrict__ given, int m) {
   constexpr bool TWO_PHASE = !RANK && (OBJ == kObjSoftmax || OBJ == kObjSelfAdv);
   constexpr bool POS_IS_SUM = !RANK && (OBJ == kObjSoftmax || OBJ == kObjBpr);
   constexpr int EPW = 64 / G;   // edges per wave
@@ -210,7 +216,8 @@ __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ po
   const int grp = lane / G, gl = lane % G;
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
   const int64_t n_waves = (int64_t)gridDim.x * 4;
-  const int64_t nk = E * (int64_t)k;
+  const int K = GIVEN ? k + m : k;   // negatives per positive
+  const int64_t nk = E * (int64_t)K;
   const bool lane_has = gl * VEC < F;   // ONE: this lane holds a piece of the row
   float lsum = 0.0f;
   for (int64_t wv = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); wv * EPW < E; wv += n_waves) {
@@ -232,7 +239,7 @@ __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ po
       if (t == 0) {
         coef[e] = __fmul_rn(w, -sig);
       } else {
-        const int64_t q = e * (int64_t)k + (t - 1);
+        const int64_t q = e * (int64_t)K + (t - 1);
         coef[E + q] = __fmul_rn(w, sig);
         neg[q] = s0;
         neg[nk + q] = idm;
@@ -260,7 +267,7 @@ __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ po
         }
         return;
       }
-      const int64_t q = e * (int64_t)k + (t - 1);
+      const int64_t q = e * (int64_t)K + (t - 1);
       neg[q] = s0;
       neg[nk + q] = idm;
       if constexpr (OBJ == kObjBpr) {
@@ -282,7 +289,7 @@ __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ po
                                                            log1pf(S_run))));
         return;
       }
-      const int64_t q = e * (int64_t)k + (t - 1);
+      const int64_t q = e * (int64_t)K + (t - 1);
       const float s = coef[E + q];
       const float p = expf(__fsub_rn(soft_arg(s, xscale), m_run)) / __fadd_rn(1.0f, S_run);
       if constexpr (OBJ == kObjSoftmax) {
@@ -297,17 +304,39 @@ __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ po
         coef[E + q] = __fmul_rn(wp, sig);
       }
     };
-    for (int t0 = 0; t0 <= k; t0 += kInFlight) {
-      // destination ids of pairs t0 .. t0 + 3: their counters span at most two Philox blocks
-      const int tf = t0 == 0 ? 1 : t0;                       // first negative of the batch (tf <= k)
-      const int tl = t0 + kInFlight - 1 < k ? t0 + kInFlight - 1 : k;
-      const uint64_t c_first = base + (uint64_t)(tf - 1);
-      const uint64_t b0 = c_first >> 2;
-      const U4 X = philox4x32_10(U4{(uint32_t)b0, (uint32_t)(b0 >> 32), 0u, 0u}, k0, k1);
-      U4 Y = X;
-      if ((int)(c_first & 3) + (tl - tf) >= 4) {
-        const uint64_t b1 = b0 + 1;
-        Y = philox4x32_10(U4{(uint32_t)b1, (uint32_t)(b1 >> 32), 0u, 0u}, k0, k1);
+    // GIVEN: the given ids of a batch are loaded one batch ahead, so that the id -> row load chain of a given pair
+    // (a drawn id comes out of the ALU) is not exposed in front of every batch's row gather
+    int32_t g_pre[kInFlight];
+    auto load_given = [&](int tb) {
+#pragma unroll
+      for (int u = 0; u < kInFlight; ++u) {
+        const int t = tb + u;
+        g_pre[u] = 0;
+        if (t > k && t <= K) g_pre[u] = given[e * (int64_t)m + (t - k - 1)];
+      }
+    };
+    if constexpr (GIVEN) load_given(0);
+    for (int t0 = 0; t0 <= K; t0 += kInFlight) {
+      int32_t g_cur[kInFlight];
+      if constexpr (GIVEN) {
+#pragma unroll
+        for (int u = 0; u < kInFlight; ++u) g_cur[u] = g_pre[u];
+        if (t0 + kInFlight <= K) load_given(t0 + kInFlight);
+      }
+      // destination ids of pairs t0 .. t0 + 3: the counters of the drawn ones span at most two Philox blocks
+      const int tf = t0 == 0 ? 1 : t0;                       // first negative of the batch (drawn iff tf <= k)
+      const int tl = t0 + kInFlight - 1 < k ? t0 + kInFlight - 1 : k;   // last drawn pair of the batch
+      uint64_t b0 = 0;
+      U4 X = U4{0u, 0u, 0u, 0u}, Y = X;
+      if (!GIVEN || tf <= k) {   // GIVEN: a batch of given pairs only (k = 0: every batch) draws nothing
+        const uint64_t c_first = base + (uint64_t)(tf - 1);
+        b0 = c_first >> 2;
+        X = philox4x32_10(U4{(uint32_t)b0, (uint32_t)(b0 >> 32), 0u, 0u}, k0, k1);
+        Y = X;
+        if ((int)(c_first & 3) + (tl - tf) >= 4) {
+          const uint64_t b1 = b0 + 1;
+          Y = philox4x32_10(U4{(uint32_t)b1, (uint32_t)(b1 >> 32), 0u, 0u}, k0, k1);
+        }
       }
       int64_t id[kInFlight];
 #pragma unroll
@@ -319,6 +348,8 @@ __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ po
           const uint32_t wx = word_of(X, (uint32_t)c & 3u), wy = word_of(Y, (uint32_t)c & 3u);
           const uint32_t r = (c >> 2) == b0 ? wx : wy;
           id[u] = reduce_range(r, n_dst);
+        } else if (GIVEN && t > k && t <= K) {
+          id[u] = g_cur[u];
         }
       }
       float sc[kInFlight];
@@ -330,7 +361,7 @@ __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ po
         for (int u = 0; u < kInFlight; ++u) {
 #pragma unroll
           for (int c = 0; c < VEC; ++c) bv[u][c] = 0.0f;
-          if (lane_has && t0 + u <= k) ld_piece<VEC>(zd + id[u] * ldd + gl * VEC, bv[u]);   // t0, k uniform
+          if (lane_has && t0 + u <= K) ld_piece<VEC>(zd + id[u] * ldd + gl * VEC, bv[u]);   // t0, K uniform
         }
 #pragma unroll
         for (int u = 0; u < kInFlight; ++u) sc[u] = dot_piece<VEC>(sc[u], av, bv[u]);
@@ -342,7 +373,7 @@ __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ po
           for (int u = 0; u < kInFlight; ++u) {
 #pragma unroll
             for (int c = 0; c < VEC; ++c) bv[u][c] = 0.0f;
-            if (t0 + u <= k) ld_piece<VEC>(zd + id[u] * ldd + f, bv[u]);
+            if (t0 + u <= K) ld_piece<VEC>(zd + id[u] * ldd + f, bv[u]);
           }
 #pragma unroll
           for (int u = 0; u < kInFlight; ++u) sc[u] = dot_piece<VEC>(sc[u], x, bv[u]);
@@ -358,20 +389,20 @@ __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ po
         for (int u = 0; u < kInFlight; ++u) {
           const int t = t0 + u;
           if (t == 0) s_pos = sc[u];
-          else if (t <= k) { gt += sc[u] > s_pos; eq += sc[u] == s_pos; }
+          else if (t <= K) { gt += sc[u] > s_pos; eq += sc[u] == s_pos; }
         }
       } else if constexpr (OBJ != kObjBce) {
         // after the shuffles every lane of the group holds the batch's four scores
         if (t0 == 0) s_pos = sc[0];
         if constexpr (TWO_PHASE) {
-          // online normaliser, pairs in order; t0, k are uniform, so masked pairs (t > k) are skipped by all lanes
+          // online normaliser, pairs in order; t0, K are uniform, so masked pairs (t > K) are skipped by all lanes
           // S_run leaves out the maximum's own term exp(0) = 1, so that log1p(S_run) keeps a loss far below 1.  One
           // exp per pair serves both cases: a new maximum turns the old one into a term and rescales by exp(m - x),
           // anything else adds exp(x - m).  First pair: m = -inf, (0 + 1) * exp(-inf) = 0.
           constexpr int T_MIN = OBJ == kObjSoftmax ? 0 : 1;
 #pragma unroll
           for (int u = 0; u < kInFlight; ++u)
-            if (t0 + u >= T_MIN && t0 + u <= k) {
+            if (t0 + u >= T_MIN && t0 + u <= K) {
               const float x = soft_arg(sc[u], xscale);
               const bool up = x > m_run;
               const float ex = expf(-fabsf(__fsub_rn(x, m_run)));
@@ -385,11 +416,11 @@ __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ po
 #pragma unroll
           for (int u = 1; u < kInFlight; ++u)
             if (gl == u) { s = sc[u]; idm = id[u]; }
-          if (valid && gl < kInFlight && t0 + gl <= k) first_pass(t0 + gl, s, idm);
+          if (valid && gl < kInFlight && t0 + gl <= K) first_pass(t0 + gl, s, idm);
         } else {
 #pragma unroll
           for (int u = 0; u < kInFlight; ++u)
-            if (writer && t0 + u <= k) first_pass(t0 + u, sc[u], id[u]);
+            if (writer && t0 + u <= K) first_pass(t0 + u, sc[u], id[u]);
         }
       } else if constexpr (G >= kInFlight) {
         // every lane holds the four scores: lane u of the group finishes pair t0 + u (one exp / log1p per batch
@@ -399,11 +430,11 @@ __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ po
 #pragma unroll
         for (int u = 1; u < kInFlight; ++u)
           if (gl == u) { s = sc[u]; idm = id[u]; }
-        if (valid && gl < kInFlight && t0 + gl <= k) finish_pair(t0 + gl, s, idm);
+        if (valid && gl < kInFlight && t0 + gl <= K) finish_pair(t0 + gl, s, idm);
       } else {
 #pragma unroll
         for (int u = 0; u < kInFlight; ++u)
-          if (writer && t0 + u <= k) finish_pair(t0 + u, sc[u], id[u]);
+          if (writer && t0 + u <= K) finish_pair(t0 + u, sc[u], id[u]);
       }
     }
     if (RANK && writer) {
@@ -414,10 +445,10 @@ __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ po
       // the (t0, u) -> lane mapping of the batch loop again: every lane reads the slots it wrote itself
       if constexpr (G >= kInFlight) {
         if (valid && gl < kInFlight)
-          for (int t = gl; t <= k; t += kInFlight) second_pass(t);
+          for (int t = gl; t <= K; t += kInFlight) second_pass(t);
       } else {
         if (writer)
-          for (int t = 0; t <= k; ++t) second_pass(t);
+          for (int t = 0; t <= K; ++t) second_pass(t);
       }
     }
     if constexpr (POS_IS_SUM) {
@@ -704,27 +735,30 @@ int link_common_checks(const char* what, const int64_t* pos, int64_t E, int64_t 
   return HGIN_OK;
 }
 
-template <bool RANK, int OBJ = kObjBce>
+// GIVEN (A18): k uniform draws + m given destinations per positive (given int32 [E, m]); otherwise m = 0.
+template <bool RANK, int OBJ = kObjBce, bool GIVEN = false>
 void launch_link_fwd(const LinkShape& sh, hipStream_t s, const int64_t* pos, int64_t E, int k, uint64_t seed,
                      uint64_t offset, uint32_t n_dst, const float* z_src, int64_t ld_src, const float* z_dst,
                      int64_t ld_dst, int F, float* coef, int64_t* neg, float* partial, int32_t* n_gt, int32_t* n_eq,
-                     float param = 0.0f) {
-  float w_pos = (float)(0.5 / (double)E), w_neg = (float)(0.5 / ((double)E * (double)k)), xscale = 0.0f;
+                     float param = 0.0f, const int32_t* given = nullptr, int m = 0) {
+  const int K = k + m;
+  float w_pos = (float)(0.5 / (double)E), w_neg = (float)(0.5 / ((double)E * (double)K)), xscale = 0.0f;
   if (OBJ == kObjSoftmax) {
     w_pos = (float)(1.0 / (double)E);
     w_neg = (float)(1.0 / ((double)param * (double)E));
     xscale = (float)(1.0 / (double)param);
   } else if (OBJ == kObjBpr) {
-    w_neg = (float)(1.0 / ((double)E * (double)k));
+    w_neg = (float)(1.0 / ((double)E * (double)K));
   } else if (OBJ == kObjSelfAdv) {
     xscale = param;
   }
   constexpr const char* kEpilogue[] = {"LOSS", "SOFTMAX", "BPR", "SELFADV"};
-  HGIN_TRACE("k_link_fwd<%d,%d,%s,%s>", sh.vec ? 4 : 1, sh.g, sh.one ? "ONE" : "LOOP", RANK ? "RANK" : kEpilogue[OBJ]);
-#define HGIN_LINK_FWD(VEC_, G_, ONE_)                                                                              \
-  k_link_fwd<VEC_, G_, ONE_, RANK, OBJ><<<sh.grid, 256, 0, s>>>(pos, E, k, seed, offset, n_dst, z_src, ld_src,     \
-                                                                z_dst, ld_dst, F, w_pos, w_neg, xscale, coef, neg, \
-                                                                partial, n_gt, n_eq)
+  HGIN_TRACE("k_link_fwd<%d,%d,%s,%s%s>", sh.vec ? 4 : 1, sh.g, sh.one ? "ONE" : "LOOP",
+             RANK ? "RANK" : kEpilogue[OBJ], GIVEN ? ",GIVEN" : "");
+#define HGIN_LINK_FWD(VEC_, G_, ONE_)                                                                                \
+  k_link_fwd<VEC_, G_, ONE_, RANK, OBJ, GIVEN><<<sh.grid, 256, 0, s>>>(pos, E, k, seed, offset, n_dst, z_src, ld_src, \
+                                                                       z_dst, ld_dst, F, w_pos, w_neg, xscale, coef,  \
+                                                                       neg, partial, n_gt, n_eq, given, m)
   if (sh.vec) {
     if (!sh.one) HGIN_LINK_FWD(4, 64, false);
     else HGIN_G_SWITCH(sh.g, HGIN_LINK_FWD(4, G, true))
@@ -822,6 +856,83 @@ extern "C" int hgin_link_rank_f32(const int64_t* pos, int64_t n_pos, int64_t k, 
   launch_link_fwd<true>(sh, as_stream(stream), pos, n_pos, (int)k, seed, offset, (uint32_t)n_dst, z_src, ld_src, z_dst,
                         ld_dst, (int)F, nullptr, nullptr, nullptr, n_greater, n_equal);
   return check_launch("hgin_link_rank_f32");
+}
+
+// ---- A18 entry points: k uniform + m given negatives per positive --------------------------------------------------
+namespace {
+
+int link_given_checks(const char* what, const int64_t* pos, int64_t E, int64_t k, int64_t n_dst, const int32_t* neg_dst,
+                      int64_t m, const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F) {
+  HGIN_ARG_CHECK(E >= 1 && E < (int64_t(1) << 31), "%s: E = %lld must be in [1, 2^31)", what, (long long)E);
+  HGIN_ARG_CHECK(k >= 0 && k < (int64_t(1) << 31), "%s: k = %lld must be >= 0", what, (long long)k);
+  HGIN_ARG_CHECK(m >= 1 && m < (int64_t(1) << 31), "%s: m = %lld must be >= 1", what, (long long)m);
+  HGIN_ARG_CHECK(E * (k + m) < (int64_t(1) << 31), "%s: E * (k + m) = %lld must be < 2^31", what,
+                 (long long)(E * (k + m)));
+  HGIN_ARG_CHECK(n_dst >= 1 && n_dst < (int64_t(1) << 31), "%s: n_dst must be in [1, 2^31)", what);
+  HGIN_ARG_CHECK(F >= 1 && F < (1 << 24), "%s: F must be in [1, 2^24)", what);
+  HGIN_ARG_CHECK(pos != nullptr, "%s: pos NULL", what);
+  HGIN_ARG_CHECK(neg_dst != nullptr, "%s: neg_dst NULL", what);
+  HGIN_ARG_CHECK(z_src != nullptr, "%s: z_src NULL", what);
+  HGIN_ARG_CHECK(z_dst != nullptr, "%s: z_dst NULL", what);
+  HGIN_ARG_CHECK(ld_src >= F && ld_dst >= F, "%s: leading dimension too small", what);
+  return HGIN_OK;
+}
+
+}  // namespace
+
+extern "C" int hgin_link_loss_fwd_neg_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64_t seed, uint64_t offset,
+                                          int64_t n_dst, const int32_t* neg_dst, int64_t m, const float* z_src,
+                                          int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F, float* coef,
+                                          int64_t* neg, float* loss, void* workspace, size_t workspace_bytes,
+                                          int32_t objective, float param, void* stream) {
+  const char* what = "hgin_link_loss_fwd_neg_f32";
+  const int rc = link_given_checks(what, pos, n_pos, k, n_dst, neg_dst, m, z_src, ld_src, z_dst, ld_dst, F);
+  if (rc != HGIN_OK) return rc;
+  HGIN_ARG_CHECK(coef != nullptr, "%s: coef NULL", what);
+  HGIN_ARG_CHECK(neg != nullptr, "%s: neg NULL", what);
+  HGIN_ARG_CHECK(loss != nullptr, "%s: loss NULL", what);
+  HGIN_ARG_CHECK(objective >= kObjBce && objective <= kObjSelfAdv, "%s: objective = %d must be in [0, 3]", what,
+                 (int)objective);
+  HGIN_ARG_CHECK(objective != kObjSoftmax || (std::isfinite(param) && param > 0.0f),
+                 "%s: temperature = %g must be finite and > 0", what, (double)param);
+  HGIN_ARG_CHECK(objective != kObjSelfAdv || (std::isfinite(param) && param >= 0.0f),
+                 "%s: alpha = %g must be finite and >= 0", what, (double)param);
+  if (workspace == nullptr || workspace_bytes < (size_t)kLinkMaxGrid * sizeof(float)) {
+    set_error("%s: workspace %zu bytes < required %zu", what, workspace_bytes, (size_t)kLinkMaxGrid * sizeof(float));
+    return HGIN_E_WORKSPACE;
+  }
+  hipStream_t s = as_stream(stream);
+  const LinkShape sh = link_shape(n_pos, F, z_src, ld_src, z_dst, ld_dst);
+  float* partial = static_cast<float*>(workspace);
+#define HGIN_LINK_NEG(OBJ_)                                                                                          \
+  launch_link_fwd<false, OBJ_, true>(sh, s, pos, n_pos, (int)k, seed, offset, (uint32_t)n_dst, z_src, ld_src, z_dst, \
+                                     ld_dst, (int)F, coef, neg, partial, nullptr, nullptr, param, neg_dst, (int)m)
+  if (objective == kObjBce) HGIN_LINK_NEG(kObjBce);
+  else if (objective == kObjSoftmax) HGIN_LINK_NEG(kObjSoftmax);
+  else if (objective == kObjBpr) HGIN_LINK_NEG(kObjBpr);
+  else HGIN_LINK_NEG(kObjSelfAdv);
+#undef HGIN_LINK_NEG
+  const int rc2 = check_launch(what);
+  if (rc2 != HGIN_OK) return rc2;
+  HGIN_TRACE("k_link_loss_sum");
+  k_link_loss_sum<<<1, 256, 0, s>>>(partial, (int)sh.grid, loss);
+  return check_launch(what);
+}
+
+extern "C" int hgin_link_rank_neg_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64_t seed, uint64_t offset,
+                                      int64_t n_dst, const int32_t* neg_dst, int64_t m, const float* z_src,
+                                      int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F,
+                                      int32_t* n_greater, int32_t* n_equal, void* stream) {
+  const char* what = "hgin_link_rank_neg_f32";
+  const int rc = link_given_checks(what, pos, n_pos, k, n_dst, neg_dst, m, z_src, ld_src, z_dst, ld_dst, F);
+  if (rc != HGIN_OK) return rc;
+  HGIN_ARG_CHECK(n_greater != nullptr, "%s: n_greater NULL", what);
+  HGIN_ARG_CHECK(n_equal != nullptr, "%s: n_equal NULL", what);
+  const LinkShape sh = link_shape(n_pos, F, z_src, ld_src, z_dst, ld_dst);
+  launch_link_fwd<true, kObjBce, true>(sh, as_stream(stream), pos, n_pos, (int)k, seed, offset, (uint32_t)n_dst, z_src,
+                                       ld_src, z_dst, ld_dst, (int)F, nullptr, nullptr, nullptr, n_greater, n_equal,
+                                       0.0f, neg_dst, (int)m);
+  return check_launch(what);
 }
 
 extern "C" int hgin_link_loss_bwd_src_f32(const int32_t* rowptr, const int32_t* col, const int32_t* perm,

@@ -175,6 +175,10 @@ _SIGS = {
                                _I32),
     "hgin_link_loss_fwd_obj_f32": ([_P, _I64, _I64, _U64, _U64, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _P, _P, _SZ,
                                     ctypes.c_int32, ctypes.c_float, _P], _I32),
+    "hgin_link_loss_fwd_neg_f32": ([_P, _I64, _I64, _U64, _U64, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _P, _P,
+                                    _SZ, ctypes.c_int32, ctypes.c_float, _P], _I32),
+    "hgin_link_rank_neg_f32": ([_P, _I64, _I64, _U64, _U64, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _P],
+                               _I32),
     "hgin_link_loss_bwd_src_f32": ([_P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _P, _I64, _P], _I32),
     "hgin_link_loss_bwd_dst_f32": ([_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _I64, _I64, _P, _I64, _P], _I32),
     "hgin_link_rank_f32": ([_P, _I64, _I64, _U64, _U64, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _P], _I32),
@@ -213,7 +217,7 @@ _SIGS = {
     "hgin_trace_enable": ([_I32], _I32),
     "hgin_trace_read": ([ctypes.c_char_p, _SZ], _SZ),
 }
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 def lib() -> ctypes.CDLL:

@@ -24,6 +24,10 @@ edges, on the fp32 matrix cores without materialising a score (csrc/hgin_linkran
 
 Prediction (A16, not in the reference): ``link_topk`` / ``LinkPredictor.predict`` return the k best destinations of
 every query source, known edges left out, from the same sweep with a selecting epilogue (csrc/hgin_linktopk.hip).
+
+Given negatives (A18, not in the reference): ``negative_edges`` / ``link_loss`` / ``sampled_link_loss`` / ``link_ranks``
+/ ``link_metrics`` take ``neg_dst`` = an integer [E, m] tensor of destinations that join each positive's k uniform draws
+(k may then be 0); ``hard_negatives`` mines such a set with ``link_topk``, ``LinkPredictor(hard=m)`` trains on it.
 """
 from __future__ import annotations
 
@@ -44,13 +48,71 @@ def sample_negative_dst(n: int, n_dst: int, seed: int, offset: int = 0, device="
     return out
 
 
-def negative_edges(edge_index: Tensor, n_dst: int, k: int, seed: int, offset: int = 0) -> Tensor:
-    """k corrupted copies of every positive edge: src kept, dst drawn uniformly."""
+def _given_shape(what: str, neg_dst, pos: Tensor) -> int:
+    """m of a caller-supplied negative set ``neg_dst`` (integer [E, m], m >= 1), 0 for None; TypeError / ValueError
+    for anything else.  Looks at shapes and dtypes only, so it runs before any device is needed."""
+    if neg_dst is None:
+        return 0
+    if not isinstance(neg_dst, Tensor) or neg_dst.dtype not in (torch.int32, torch.int64):
+        got = neg_dst.dtype if isinstance(neg_dst, Tensor) else type(neg_dst).__name__
+        raise TypeError(f"{what}: neg_dst must be an int32 or int64 tensor, got {got}")
+    E = int(pos.size(1)) if pos.dim() == 2 else -1
+    if neg_dst.dim() != 2 or int(neg_dst.size(0)) != E or int(neg_dst.size(1)) < 1:
+        raise ValueError(f"{what}: neg_dst must be [E, m] with E = {E} and m >= 1, got {tuple(neg_dst.shape)}")
+    return int(neg_dst.size(1))
+
+
+def _mark_checked(neg32: Tensor, n_dst: int) -> None:
+    """Record on an int32 contiguous set that its values are known to lie in [0, n_dst)."""
+    try:
+        neg32._hgin_neg_dst = (neg32._version, {int(n_dst): neg32})
+    except (AttributeError, RuntimeError):
+        pass
+
+
+def _given_negatives(what: str, neg_dst: Tensor, n_dst: int) -> Tensor:
+    """``neg_dst`` as the kernels read it: int32, contiguous (an int32 contiguous tensor is passed as it is), values
+    range-checked against [0, n_dst) (one host sync; IndexError) once per tensor version and cached on the tensor,
+    the way ``_known_csr`` does it."""
+    ops.require_device(neg_dst, what=what)
+    key = int(n_dst)
+    cache = getattr(neg_dst, "_hgin_neg_dst", None)
+    ver = neg_dst._version
+    if cache is not None and cache[0] == ver and key in cache[1]:
+        return cache[1][key]
+    lo, hi = torch.stack([neg_dst.amin(), neg_dst.amax()]).tolist()
+    if lo < 0 or hi >= n_dst:
+        raise IndexError(f"{what}: neg_dst index out of range [0, {n_dst})")
+    out = neg_dst if neg_dst.dtype == torch.int32 and neg_dst.is_contiguous() else neg_dst.to(torch.int32).contiguous()
+    if cache is None or cache[0] != ver:
+        cache = (ver, {})
+    cache[1][key] = out
+    try:
+        neg_dst._hgin_neg_dst = cache
+    except (AttributeError, RuntimeError):
+        pass
+    return out
+
+
+def negative_edges(edge_index: Tensor, n_dst: int, k: int, seed: int, offset: int = 0,
+                   neg_dst: Tensor = None) -> Tensor:
+    """k corrupted copies of every positive edge: src kept, dst drawn uniformly.  With ``neg_dst``
+    (integer [E, m]; include/hgin.h A18) every positive gets k + m copies, destinations [k drawn | m given]; k may be
+    0."""
+    m = _given_shape("negative_edges", neg_dst, edge_index)
     ops.require_device(edge_index, what="negative_edges")
     E = int(edge_index.size(1))
-    dst = sample_negative_dst(E * k, n_dst, seed, offset, edge_index.device).long()
-    src = edge_index[0].repeat_interleave(k)
-    return torch.stack([src, dst])
+    if m == 0:
+        dst = sample_negative_dst(E * k, n_dst, seed, offset, edge_index.device).long()
+        src = edge_index[0].repeat_interleave(k)
+        return torch.stack([src, dst])
+    k = int(k)
+    if k < 0 or E * (k + m) >= 2**31:
+        raise ValueError(f"negative_edges: need k >= 0 and E * (k + m) < 2^31 (E = {E}, k = {k}, m = {m})")
+    given = _given_negatives("negative_edges", neg_dst, n_dst)
+    drawn = sample_negative_dst(E * k, n_dst, seed, offset, edge_index.device).view(E, k)
+    dst = torch.cat([drawn, given], 1).reshape(-1).long()
+    return torch.stack([edge_index[0].repeat_interleave(k + m), dst])
 
 
 class _DotDecodeFn(torch.autograd.Function):
@@ -118,12 +180,15 @@ def _objective(what: str, objective, temperature, alpha):
 
 
 def link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0, objective: str = "bce",
-              temperature: float = 1.0, alpha: float = 1.0) -> Tensor:
+              temperature: float = 1.0, alpha: float = 1.0, neg_dst: Tensor = None) -> Tensor:
     """The unfused sampled link loss over positives and k uniform negatives per positive: ``objective`` "bce"
     (BCE-with-logits, the default), "softmax", "bpr" or "selfadv" (include/hgin.h A17), as torch ops on the two
-    ``dot_decode`` score vectors."""
+    ``dot_decode`` score vectors.  ``neg_dst`` (integer [E, m]) adds m given negatives per positive (A18)."""
     code, param = _objective("link_loss", objective, temperature, alpha)
-    neg = negative_edges(pos, z_dst.size(0), k, seed, offset)
+    m = _given_shape("link_loss", neg_dst, pos)
+    neg = negative_edges(pos, z_dst.size(0), k, seed, offset) if m == 0 else \
+        negative_edges(pos, z_dst.size(0), k, seed, offset, neg_dst)
+    k = int(k) + m
     s_pos = dot_decode(z_src, z_dst, pos)
     s_neg = dot_decode(z_src, z_dst, neg)
     fn = torch.nn.functional
@@ -143,9 +208,13 @@ def link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offs
 # ---------------------------------------------------------------------------------------------------
 # A13 / A14: the fused sampled link loss, sampled ranks and the training head (NOT IN REFERENCE)
 # ---------------------------------------------------------------------------------------------------
-def _link_operands(what: str, z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int):
-    """Checked operands of the fused kernels: fp32 row-major embeddings of one width, validated positives."""
-    ops.require_device(z_src, z_dst, pos, what=what)
+def _link_operands(what: str, z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, neg_dst: Tensor = None):
+    """Checked operands of the fused kernels: fp32 row-major embeddings of one width, validated positives; with
+    ``neg_dst`` the checked int32 [E, m] set comes back as a seventh item (and k may be 0)."""
+    m = _given_shape(what, neg_dst, pos)
+    if int(k) < (0 if m else 1):
+        raise ValueError(f"{what}: need E >= 1, k >= {0 if m else 1} and E * k < 2^31 (k = {int(k)})")
+    ops.require_device(z_src, z_dst, pos, neg_dst, what=what)
     for name, z in (("z_src", z_src), ("z_dst", z_dst)):
         if z.dtype != torch.float32:
             raise TypeError(f"{what}: {name} must be float32 (the fused link kernels are fp32 only), got {z.dtype}")
@@ -155,11 +224,15 @@ def _link_operands(what: str, z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int)
         raise RuntimeError(f"{what}: embedding widths differ")
     ops.check_edge_index(pos)
     E, k = int(pos.size(1)), int(k)
-    if E < 1 or k < 1 or E * k >= 2**31:
+    if m:
+        if E < 1 or E * (k + m) >= 2**31:
+            raise ValueError(f"{what}: need E >= 1, k >= 0 and E * (k + m) < 2^31 (E = {E}, k = {k}, m = {m})")
+    elif E < 1 or k < 1 or E * k >= 2**31:
         raise ValueError(f"{what}: need E >= 1, k >= 1 and E * k < 2^31 (E = {E}, k = {k})")
     # the static CSR / CSC of the positives: built (and range-checked) once per pos tensor, cached on it
     graph = ops.relation_graph(pos, z_src.size(0), z_dst.size(0))
-    return ops._rowmajor(z_src), ops._rowmajor(z_dst), pos.contiguous(), graph, E, k
+    out = (ops._rowmajor(z_src), ops._rowmajor(z_dst), pos.contiguous(), graph, E, k)
+    return out if m == 0 else out + (_given_negatives(what, neg_dst, int(z_dst.size(0))),)
 
 
 _SIDE_STREAMS: dict = {}
@@ -177,15 +250,22 @@ def _side_stream(device) -> "torch.cuda.Stream":
 class _SampledLinkLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z_src, z_dst, pos, graph: ops.RelationGraph, k: int, seed: int, offset: int, objective: int = 0,
-                param: float = 0.0):
+                param: float = 0.0, neg_dst: Tensor = None):
         E, F, dev = int(pos.size(1)), int(z_src.size(1)), z_src.device
-        coef = torch.empty(E * (1 + k), dtype=torch.float32, device=dev)
-        neg = torch.empty((2, E * k), dtype=torch.int64, device=dev)
+        m = 0 if neg_dst is None else int(neg_dst.size(1))   # A18: k uniform + m given negatives per positive
+        K = k + m
+        coef = torch.empty(E * (1 + K), dtype=torch.float32, device=dev)
+        neg = torch.empty((2, E * K), dtype=torch.int64, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         nbytes = ctypes.c_size_t(0)
         _lib.check(_lib.lib().hgin_link_loss_workspace_size(E, ctypes.byref(nbytes)), "hgin_link_loss_workspace_size")
         ws = ops._workspace(nbytes.value, dev)
-        if objective == 0:
+        if m:   # the same coef / neg layout with K in place of k: the backward below does not know the difference
+            _lib.call("hgin_link_loss_fwd_neg_f32", ops._p(pos), E, k, int(seed) & (2**64 - 1),
+                      int(offset) & (2**64 - 1), int(z_dst.size(0)), ops._p(neg_dst), m, ops._p(z_src), z_src.stride(0),
+                      ops._p(z_dst), z_dst.stride(0), F, ops._p(coef), ops._p(neg), ops._p(loss), ops._p(ws),
+                      nbytes.value, objective, param, ops._stream(loss))
+        elif objective == 0:
             _lib.call("hgin_link_loss_fwd_f32", ops._p(pos), E, k, int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
                       int(z_dst.size(0)), ops._p(z_src), z_src.stride(0), ops._p(z_dst), z_dst.stride(0), F,
                       ops._p(coef), ops._p(neg), ops._p(loss), ops._p(ws), nbytes.value, ops._stream(loss))
@@ -194,7 +274,7 @@ class _SampledLinkLossFn(torch.autograd.Function):
                       int(offset) & (2**64 - 1), int(z_dst.size(0)), ops._p(z_src), z_src.stride(0), ops._p(z_dst),
                       z_dst.stride(0), F, ops._p(coef), ops._p(neg), ops._p(loss), ops._p(ws), nbytes.value,
                       objective, param, ops._stream(loss))
-        ctx.graph, ctx.k = graph, k
+        ctx.graph, ctx.k = graph, K
         ctx.save_for_backward(coef, neg, z_src, z_dst)
         return loss.reshape(())
 
@@ -241,29 +321,48 @@ class _SampledLinkLossFn(torch.autograd.Function):
             _lib.call("hgin_link_loss_bwd_dst_f32", ops._p(csr.rowptr), ops._p(csr.col), ops._p(csr.perm),
                       ops._p(nrow), ops._p(ncol), ops._p(nperm), n_dst, E, ops._p(g), ops._p(coef), ops._p(z_src),
                       z_src.stride(0), F, ops._p(g_dst), g_dst.stride(0), ops._stream(g))
-        return g_src, g_dst, None, None, None, None, None, None, None
+        return g_src, g_dst, None, None, None, None, None, None, None, None
 
 
 def sampled_link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0,
-                      objective: str = "bce", temperature: float = 1.0, alpha: float = 1.0) -> Tensor:
+                      objective: str = "bce", temperature: float = 1.0, alpha: float = 1.0,
+                      neg_dst: Tensor = None) -> Tensor:
     """``link_loss`` in fused form (include/hgin.h A13 / A17): the same pairs (``negative_edges(pos, n_dst, k, seed,
     offset)``) and the same loss, one forward pass that draws the negatives in the kernel and reads every source
     row once, and a deterministic store-and-sum backward (static CSC / CSR of ``pos`` + one sort of the step's
     negatives).  ``objective``: "bce" (default), "softmax" (InfoNCE over the positive and its k negatives at
     ``temperature``), "bpr" (pairwise) or "selfadv" (BCE with the negatives weighted by a detached
-    softmax(``alpha`` * score)); only the forward epilogue differs.  Returns a scalar; fp32 embeddings only."""
+    softmax(``alpha`` * score)); only the forward epilogue differs.  ``neg_dst`` (int32 or int64 [E, m] on the device,
+    values in [0, n_dst): checked once per tensor version, one host sync) adds m given negatives after each
+    positive's k drawn ones (include/hgin.h A18): K = k + m takes k's place in every weight and normaliser, k may be
+    0, and a given destination contributes exactly what the same destination would as a draw.  Returns a scalar; fp32
+    embeddings only."""
     code, param = _objective("sampled_link_loss", objective, temperature, alpha)
-    z_src, z_dst, pos, graph, _, k = _link_operands("sampled_link_loss", z_src, z_dst, pos, k)
-    return _SampledLinkLossFn.apply(z_src, z_dst, pos, graph, k, int(seed), int(offset), code, param)
+    if neg_dst is None:
+        z_src, z_dst, pos, graph, _, k = _link_operands("sampled_link_loss", z_src, z_dst, pos, k)
+        return _SampledLinkLossFn.apply(z_src, z_dst, pos, graph, k, int(seed), int(offset), code, param)
+    z_src, z_dst, pos, graph, _, k, given = _link_operands("sampled_link_loss", z_src, z_dst, pos, k, neg_dst)
+    return _SampledLinkLossFn.apply(z_src, z_dst, pos, graph, k, int(seed), int(offset), code, param, given)
 
 
-def link_ranks(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0):
+def link_ranks(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0, neg_dst: Tensor = None):
     """(n_greater, n_equal), int32 [E]: how many of each positive's k sampled negatives (the draws of
-    ``sampled_link_loss``) score above / exactly equal to it (include/hgin.h A14).  No gradient."""
-    z_src, z_dst, pos, _, E, k = _link_operands("link_ranks", z_src, z_dst, pos, k)
+    ``sampled_link_loss``) score above / exactly equal to it (include/hgin.h A14); with ``neg_dst`` (integer [E, m],
+    e.g. a fixed evaluation set; A18) the counts cover the k draws and the m given negatives, and k may be 0.  No
+    gradient."""
+    given = None
+    if neg_dst is None:
+        z_src, z_dst, pos, _, E, k = _link_operands("link_ranks", z_src, z_dst, pos, k)
+    else:
+        z_src, z_dst, pos, _, E, k, given = _link_operands("link_ranks", z_src, z_dst, pos, k, neg_dst)
     z_src, z_dst = z_src.detach(), z_dst.detach()
     n_gt = torch.empty(E, dtype=torch.int32, device=z_src.device)
     n_eq = torch.empty(E, dtype=torch.int32, device=z_src.device)
+    if given is not None:
+        _lib.call("hgin_link_rank_neg_f32", ops._p(pos), E, k, int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
+                  int(z_dst.size(0)), ops._p(given), int(given.size(1)), ops._p(z_src), z_src.stride(0), ops._p(z_dst),
+                  z_dst.stride(0), int(z_src.size(1)), ops._p(n_gt), ops._p(n_eq), ops._stream(n_gt))
+        return n_gt, n_eq
     _lib.call("hgin_link_rank_f32", ops._p(pos), E, k, int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
               int(z_dst.size(0)), ops._p(z_src), z_src.stride(0), ops._p(z_dst), z_dst.stride(0), int(z_src.size(1)),
               ops._p(n_gt), ops._p(n_eq), ops._stream(n_gt))
@@ -283,11 +382,17 @@ def metrics_from_ranks(n_greater: Tensor, n_equal: Tensor, k: int) -> dict:
     return out
 
 
-def link_metrics(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0) -> dict:
+def link_metrics(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0,
+                 neg_dst: Tensor = None) -> dict:
     """auc / mrr / hits@1 / hits@3 / hits@10 of the positives against k sampled negatives each, as device scalars
-    (float64): the ranking kernel + a few reductions over [E]; no host sync before the caller reads a value."""
-    n_gt, n_eq = link_ranks(z_src, z_dst, pos, k, seed, offset)
-    return metrics_from_ranks(n_gt, n_eq, k)
+    (float64): the ranking kernel + a few reductions over [E]; no host sync before the caller reads a value.  With
+    ``neg_dst`` (integer [E, m]; A18) against the k draws and the m given negatives (the set's one-off range check
+    aside)."""
+    if neg_dst is None:
+        n_gt, n_eq = link_ranks(z_src, z_dst, pos, k, seed, offset)
+        return metrics_from_ranks(n_gt, n_eq, k)
+    n_gt, n_eq = link_ranks(z_src, z_dst, pos, k, seed, offset, neg_dst)
+    return metrics_from_ranks(n_gt, n_eq, int(k) + int(neg_dst.size(1)))
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -428,40 +533,117 @@ def link_topk(z_src: Tensor, z_dst: Tensor, src: Tensor, k: int, known: Tensor =
     return idx, score
 
 
+def hard_negatives(z_src: Tensor, z_dst: Tensor, pos: Tensor, m: int, known: Tensor = None, seed: int = 0,
+                   offset: int = 0) -> Tensor:
+    """int32 [E, m] (include/hgin.h A18's ``neg_dst``): for every positive (s, d) of ``pos`` the m best-scoring
+    destinations of s that are not an edge of ``known`` (an edge index [2, M]; default: ``pos`` itself), best first
+    (score descending, index ascending): ``link_topk`` on the unique sources of ``pos``, gathered back per positive.
+    A source with fewer than m such destinations leaves padded slots; slot (e, j) is then filled with the uniform
+    draw ``sample_negative_dst(E * m, n_dst, seed, offset)[e * m + j]``, which is not filtered and may be a known
+    edge.  1 <= m <= 128.  No gradient."""
+    what = "hard_negatives"
+    m = int(m)
+    if not 1 <= m <= TOPK_MAX:
+        raise ValueError(f"{what}: need 1 <= m <= {TOPK_MAX}, got m = {m}")
+    ops.check_edge_index(pos)
+    E, n_dst = int(pos.size(1)), int(z_dst.size(0))
+    if E < 1 or E * m >= 2**31:
+        raise ValueError(f"{what}: need E >= 1 and E * m < 2^31 (E = {E}, m = {m})")
+    ops.require_device(z_src, z_dst, pos, known, what=what)
+    src, inverse = torch.unique(pos[0], return_inverse=True)
+    idx, _ = link_topk(z_src, z_dst, src, m, pos if known is None else known)
+    mined = idx[inverse]
+    fill = sample_negative_dst(E * m, n_dst, seed, offset, mined.device).view(E, m)
+    out = torch.where(mined < 0, fill, mined).contiguous()
+    _mark_checked(out, n_dst)   # in range by construction: no range-check sync when the set is used
+    return out
+
+
 class LinkPredictor:
     """Link-prediction head over a model's node embeddings: ``relation`` = (src_type, name, dst_type), k uniform
     negatives per positive, dot-product decoder, and the training objective of ``sampled_link_loss`` ("bce" by
     default; "softmax" with ``temperature``, "bpr", "selfadv" with ``alpha``).  The objective only shapes ``loss``;
-    ``metrics``, ``full_metrics`` and ``predict`` do not depend on it."""
+    ``metrics``, ``full_metrics`` and ``predict`` do not depend on it.
+
+    ``hard`` = m > 0 adds m mined negatives per positive (``hard_negatives``, filtered by the relation's edges) to
+    the k uniform ones, and k may then be 0.  The set is kept as ``self.neg_dst``; ``loss`` re-mines it from the
+    step's own embeddings every ``mine_every`` steps (0: only ``mine`` changes it once it exists)."""
 
     def __init__(self, model, relation, k: int, seed: int, objective: str = "bce", temperature: float = 1.0,
-                 alpha: float = 1.0):
+                 alpha: float = 1.0, hard: int = 0, mine_every: int = 1):
         if not hasattr(model, "encode"):
             raise TypeError("LinkPredictor: the model has no encode(x_dict, edge_index_dict)")
         _objective("LinkPredictor", objective, temperature, alpha)
+        hard, mine_every = int(hard), int(mine_every)
+        if not 0 <= hard <= TOPK_MAX:
+            raise ValueError(f"LinkPredictor: hard must be in [0, {TOPK_MAX}], got {hard}")
+        if mine_every < 0:
+            raise ValueError(f"LinkPredictor: mine_every must be >= 0, got {mine_every}")
+        if int(k) < (0 if hard else 1):
+            raise ValueError(f"LinkPredictor: need k >= 1, or k >= 0 with hard >= 1 (k = {int(k)}, hard = {hard})")
         self.model, self.relation, self.k, self.seed = model, tuple(relation), int(k), int(seed)
         self.objective, self.temperature, self.alpha = objective, float(temperature), float(alpha)
+        self.hard, self.mine_every = hard, mine_every
+        self.neg_dst = None       # the mined set, int32 [E, hard], of the positives self._mined_for
+        self._mined_for = None
 
     def _pos(self, graph, pos):
         return graph.edge_index[self.relation] if pos is None else pos
 
+    def _mine(self, z, graph, pos, known, offset):
+        """Padded slots are filled from the stream of seed + 1, apart from the uniform negatives' (seed)."""
+        if known is None:
+            known = graph.edge_index[self.relation]
+        self.neg_dst = hard_negatives(z[self.relation[0]].detach(), z[self.relation[2]].detach(), pos, self.hard,
+                                      known, self.seed + 1, offset)
+        self._mined_for = pos
+        return self.neg_dst
+
     def loss(self, graph, pos: Tensor = None, step: int = 0) -> Tensor:
         """The sampled loss of ``pos`` (default: the relation's own edges); step s draws the negatives at
-        offset s * E * k, so every step sees fresh ones."""
+        offset s * E * k, so every step sees fresh ones.  With ``hard`` > 0 the mined set joins them; it is mined
+        again from this step's embeddings (detached; no second encode) when ``mine_every`` > 0 divides the step, or
+        when there is none for this ``pos`` yet (padded slots: draws at offset s * E * hard)."""
         pos = self._pos(graph, pos)
         z = self.model.encode(graph.x_dict(), graph.edge_index_dict())
         offset = int(step) * int(pos.size(1)) * self.k
+        if self.hard == 0:
+            return sampled_link_loss(z[self.relation[0]], z[self.relation[2]], pos, self.k, self.seed, offset,
+                                     self.objective, self.temperature, self.alpha)
+        if self.neg_dst is None or self._mined_for is not pos or \
+                (self.mine_every > 0 and int(step) % self.mine_every == 0):
+            self._mine(z, graph, pos, None, int(step) * int(pos.size(1)) * self.hard)
         return sampled_link_loss(z[self.relation[0]], z[self.relation[2]], pos, self.k, self.seed, offset,
-                                 self.objective, self.temperature, self.alpha)
+                                 self.objective, self.temperature, self.alpha, neg_dst=self.neg_dst)
 
-    def metrics(self, graph, pos: Tensor = None) -> dict:
-        """``link_metrics`` of the model's embeddings in eval mode, without gradients (the mode is restored)."""
+    def mine(self, graph, pos: Tensor = None, known: Tensor = None) -> Tensor:
+        """Mine ``self.neg_dst`` now, from an eval-mode encode without gradients (the mode is restored), as
+        ``metrics`` encodes: ``hard`` negatives per positive of ``pos`` (default: the relation's own edges), filtered
+        by ``known`` (default: the relation's own edges).  Returns the set."""
+        if self.hard == 0:
+            raise ValueError("LinkPredictor.mine: the predictor was built with hard = 0")
         pos = self._pos(graph, pos)
         was_training = self.model.training
         self.model.eval()
         try:
             with torch.no_grad():
                 z = self.model.encode(graph.x_dict(), graph.edge_index_dict())
+                return self._mine(z, graph, pos, known, 0)
+        finally:
+            self.model.train(was_training)
+
+    def metrics(self, graph, pos: Tensor = None, neg_dst: Tensor = None) -> dict:
+        """``link_metrics`` of the model's embeddings in eval mode, without gradients (the mode is restored);
+        ``neg_dst`` (integer [E, m]) is an evaluation set ranked along with the k uniform draws."""
+        pos = self._pos(graph, pos)
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                z = self.model.encode(graph.x_dict(), graph.edge_index_dict())
+                if neg_dst is not None:
+                    return link_metrics(z[self.relation[0]], z[self.relation[2]], pos, self.k, self.seed,
+                                        neg_dst=neg_dst)
                 return link_metrics(z[self.relation[0]], z[self.relation[2]], pos, self.k, self.seed)
         finally:
             self.model.train(was_training)

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HGIN_ABI_VERSION 12
+#define HGIN_ABI_VERSION 13
 
 #define HGIN_OK 0
 #define HGIN_E_ARG (-1)        /* bad size / null pointer / unsupported combination */
@@ -513,6 +513,39 @@ int hgin_link_loss_fwd_obj_f32(const int64_t* pos, int64_t n_pos, int64_t k, uin
                                int64_t n_dst, const float* z_src, int64_t ld_src, const float* z_dst,
                                int64_t ld_dst, int64_t F, float* coef, int64_t* neg, float* loss, void* workspace,
                                size_t workspace_bytes, int32_t objective, float param, void* stream);
+
+/* ---- A18: caller-supplied negatives in the fused link loss and ranks (NOT IN REFERENCE; build-defined, ABI 13) ---
+ * hgin_link_loss_fwd_neg_f32 / hgin_link_rank_neg_f32 are hgin_link_loss_fwd_obj_f32 / hgin_link_rank_f32 with
+ * K = k + m negatives per positive, of which the caller supplies m: neg_dst int32 [E, m], row-major, destination ids
+ * into z_dst; the caller guarantees 0 <= neg_dst < n_dst, as it does for pos (device data is not checked here).
+ *
+ *   pair t of positive e  | destination                                  | coefficient slot    | neg column
+ *   ----------------------+----------------------------------------------+---------------------+------------
+ *   t = 0                 | pos[1, e]                                    | coef[e]             | -
+ *   t = 1 .. k            | draw(offset + e k + t - 1), A13's counter    | coef[E + e K + t-1] | e K + t - 1
+ *                         | rule with the uniform count k                |                     |
+ *   t = k + 1 .. k + m    | neg_dst[e m + t - k - 1]                     | coef[E + e K + t-1] | e K + t - 1
+ *
+ * The drawn part is bit for bit hgin_neg_sample(seed, offset, E k, n_dst); k = 0 draws nothing (no Philox block is
+ * evaluated).  neg is int64 [2, E K] (row 0 = pos[0, e] repeated K times, row 1 = [k drawn | m given] per positive),
+ * coef is float [E + E K].  K takes k's place in everything A13 / A14 / A17 define: the weights (bce 0.5 / (E K),
+ * bpr 1 / (E K); softmax 1 / (tau E) and selfadv 0.5 / E do not depend on it), the softmax and selfadv normalisers run
+ * over all K negatives, a softmax / bpr positive's coefficient is minus the sum of its K stored ones, the rank counts
+ * cover all K negatives.  Pairs are still taken in batches of four, t = 0 first, lane u of a group finishing pair
+ * t0 + u, and a batch may hold drawn and given pairs side by side; scores, loss terms and their summation order are
+ * those of A13 / A17, so with equal destinations a given pair carries the bits of a drawn one: (k, neg_dst) and
+ * (0, [draws | neg_dst]) agree bitwise, and (0, the K draws) agrees with hgin_link_loss_fwd_obj_f32 at k = K.
+ * Backward: hgin_link_loss_bwd_src_f32 / hgin_link_loss_bwd_dst_f32 with K in place of k, on the coef / neg written here.
+ * objective / param as A17 (0 = bce included).  Workspace: hgin_link_loss_workspace_size.  E >= 1, k >= 0, m >= 1,
+ * E (k + m) < 2^31, other ranges and status codes as A17; HGIN_E_ARG for neg_dst = NULL. */
+int hgin_link_loss_fwd_neg_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64_t seed, uint64_t offset,
+                               int64_t n_dst, const int32_t* neg_dst, int64_t m, const float* z_src, int64_t ld_src,
+                               const float* z_dst, int64_t ld_dst, int64_t F, float* coef, int64_t* neg, float* loss,
+                               void* workspace, size_t workspace_bytes, int32_t objective, float param, void* stream);
+int hgin_link_rank_neg_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64_t seed, uint64_t offset,
+                           int64_t n_dst, const int32_t* neg_dst, int64_t m, const float* z_src, int64_t ld_src,
+                           const float* z_dst, int64_t ld_dst, int64_t F, int32_t* n_greater, int32_t* n_equal,
+                           void* stream);
 
 /* ---- A15: full-candidate filtered ranking (NOT IN REFERENCE; build-defined, ABI 10) ----------------------------
  * For query q (s = pos[0, q], d = pos[1, q]; pos int64 [2, E] as in A13) and score(q, c) = <z_src[s], z_dst[c]>, the

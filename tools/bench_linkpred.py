@@ -16,7 +16,16 @@ backward against ``link_loss`` with the same objective, timed like the bce pair 
 repeat loop, reported under the shape's "objectives" with the ratio to the fused bce step of the same run ("all" runs
 bce too, whose rows are produced as without the option).
 
+``--hard M`` (include/hgin.h A18) times the given-negative path instead, per shape in one run with the paths
+alternating: the fused step with k uniform + M given negatives (random in-range destinations) against the fused step
+with k + M uniform negatives (the same pair count, through the entry points that existed before A18); the same pair
+with the M negatives mined by ``hard_negatives`` from the (random) embeddings; each step's destination side alone
+(forward + the sort of the step's negatives + ``k_link_bwd_dst``: only z_dst asks for a gradient); and the mining call
+alone.  Mining sweeps every destination for every distinct source, so the mined pair uses positives whose sources come
+from the first ``--mine-sources`` source rows (the random-given pair keeps the shape's own positives).
+
     python tools/bench_linkpred.py --out profiles/linkpred/linkpred_bench.json
+    python tools/bench_linkpred.py --k 1 --hard 4 --out profiles/linkpred/linkhard_bench.json
     python tools/bench_linkpred.py --objective all --out profiles/linkpred/linkobj_bench.json
     python tools/bench_linkpred.py --configs cfg1 --scale 0.1 --k 1      # a tiny run
 """
@@ -186,6 +195,68 @@ def run_shape(torch, shape, repeats, warmup, target_ms, seed=1234, objectives=("
     return out
 
 
+def run_hard(torch, shape, M, repeats, warmup, target_ms, mine_sources, seed=1234):
+    """The ``--hard M`` measurements of one shape (module docstring)."""
+    from hgin.linkpred import hard_negatives, sampled_link_loss
+    dev = "cuda"
+    n_src, n_dst, E, F, k = (shape[x] for x in ("n_src", "n_dst", "E", "F", "k"))
+    g = torch.Generator(device=dev).manual_seed(seed)
+    pos = torch.stack([torch.randint(0, n_src, (E,), generator=g, device=dev),
+                       torch.randint(0, n_dst, (E,), generator=g, device=dev)])
+    q = min(n_src, mine_sources)
+    pos_m = torch.stack([torch.randint(0, q, (E,), generator=g, device=dev), pos[1].clone()])
+    z_src = torch.randn(n_src, F, generator=g, device=dev) * 0.1
+    z_dst = torch.randn(n_dst, F, generator=g, device=dev) * 0.1
+    given = torch.randint(0, n_dst, (E, M), generator=g, device=dev, dtype=torch.int32)
+
+    def mine(step):
+        return hard_negatives(z_src, z_dst, pos_m, M, seed=seed, offset=step * E * M)
+
+    mined = mine(0)
+    torch.cuda.synchronize()
+    counts = torch.bincount(mined.reshape(-1).long(), minlength=n_dst)
+    out = dict(shape, hard=M, mine_sources=q,
+               mined_distinct_destinations=int((counts > 0).sum()), mined_max_pairs_per_destination=int(counts.max()),
+               uniform_expected_pairs_per_destination=E * M / n_dst)
+
+    def step_of(p, kk, neg_dst, src_grad):
+        kw = {} if neg_dst is None else {"neg_dst": neg_dst}
+
+        def fn(step):
+            a, b = z_src.requires_grad_(src_grad), z_dst.requires_grad_(True)
+            a.grad = b.grad = None
+            sampled_link_loss(a, b, p, kk, seed, step * E * kk, **kw).backward()
+        return fn
+
+    paths = {"given_random": step_of(pos, k, given, True), "uniform": step_of(pos, k + M, None, True),
+             "given_mined": step_of(pos_m, k, mined, True), "uniform_mined_pos": step_of(pos_m, k + M, None, True),
+             "given_random_dst_only": step_of(pos, k, given, False),
+             "uniform_dst_only": step_of(pos, k + M, None, False),
+             "given_mined_dst_only": step_of(pos_m, k, mined, False),
+             "uniform_mined_pos_dst_only": step_of(pos_m, k + M, None, False), "mining": mine}
+    for s in range(warmup):
+        for name, fn in paths.items():
+            if name != "mining":
+                fn(s)
+    torch.cuda.synchronize()
+    inner = {name: 1 if name == "mining" else _inner_for(torch, fn, target_ms) for name, fn in paths.items()}
+    times, step = {name: [] for name in paths}, warmup
+    for _ in range(repeats):      # every path alternates
+        for name, fn in paths.items():
+            times[name].append(_timed(torch, fn, inner[name], step))
+        step += max(inner.values())
+    for name in paths:
+        out[name] = dict(_stats(times[name]), inner=inner[name])
+    for a, b in (("given_random", "uniform"), ("given_mined", "uniform_mined_pos"),
+                 ("given_random_dst_only", "uniform_dst_only"), ("given_mined_dst_only", "uniform_mined_pos_dst_only")):
+        out[f"{a}_over_{b}"] = out[a]["median_ms"] / out[b]["median_ms"]
+        out[f"{a}_within_spread_of_{b}"] = out[a]["min_ms"] <= out[b]["max_ms"] and out[b]["min_ms"] <= out[a]["max_ms"]
+    z_src.grad = z_dst.grad = None
+    del z_src, z_dst, pos, pos_m, given, mined
+    torch.cuda.empty_cache()
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--configs", default="cfg2,cfg3")
@@ -195,10 +266,15 @@ def main(argv=None) -> int:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--target-ms", type=float, default=30.0, help="device time of one timed repeat, at least")
     ap.add_argument("--objective", default="bce", help="bce, softmax, bpr, selfadv or all (include/hgin.h A17)")
+    ap.add_argument("--hard", type=int, default=None,
+                    help="time k uniform + M given / mined negatives against k + M uniform ones (include/hgin.h A18)")
+    ap.add_argument("--mine-sources", type=int, default=65536, help="--hard: distinct sources of the mined positives")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     if args.repeats < 5:
         ap.error("--repeats must be at least 5")
+    if args.hard is not None and not 1 <= args.hard <= 128:
+        ap.error("--hard must be in [1, 128]")
     objectives = objectives_of(args.objective)
     shapes = plan(args.configs.split(","), [int(v) for v in args.k.split(",")], args.scale)
     for s in shapes:
@@ -210,6 +286,17 @@ def main(argv=None) -> int:
         return 2
     from hgin import _lib
     _lib.lib()
+    if args.hard is not None:
+        results = [run_hard(torch, s, args.hard, args.repeats, args.warmup, args.target_ms, args.mine_sources)
+                   for s in shapes]
+        doc = {"tool": "tools/bench_linkpred.py", "device": torch.cuda.get_device_name(0), "repeats": args.repeats,
+               "warmup": args.warmup, "hard": args.hard, "shapes": results}
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(json.dumps(doc, indent=1) + "\n")
+        print(json.dumps(doc))
+        return 0
     results = [run_shape(torch, s, args.repeats, args.warmup, args.target_ms, objectives=objectives) for s in shapes]
     pairs = [r for r in results if "link_loss" in r] + [p for r in results for p in r.get("objectives", {}).values()]
     both = [p for p in pairs if "error" not in p["link_loss"]]
