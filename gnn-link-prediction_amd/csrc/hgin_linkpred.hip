@@ -63,6 +63,43 @@ __global__ __launch_bounds__(256) void k_neg_sample(uint64_t seed, uint64_t offs
   }
 }
 
+// A19: the segment of a source row: g = src_seg[s] clamped into [0, n_graphs), destinations [lo, lo + n) = dst_ptr[g],
+// dst_ptr[g + 1].  One src_seg load and two dst_ptr loads.
+__device__ __forceinline__ void seg_of(const int32_t* __restrict__ src_seg, const int32_t* __restrict__ dst_ptr,
+                                       int n_graphs, int64_t s, uint32_t& lo, uint32_t& n) {
+  int g = src_seg[s];
+  g = g < 0 ? 0 : (g >= n_graphs ? n_graphs - 1 : g);
+  const int32_t a = dst_ptr[g], b = dst_ptr[g + 1];
+  lo = (uint32_t)a;
+  n = b > a ? (uint32_t)(b - a) : 0u;
+}
+
+// A19 draw: lo + hi32(word * n), kept below n_dst (an empty last segment would otherwise name row n_dst)
+__device__ __forceinline__ int32_t reduce_seg(uint32_t x, uint32_t lo, uint32_t n, uint32_t n_dst) {
+  const uint32_t v = lo + (uint32_t)reduce_range(x, n);
+  return (int32_t)(v < n_dst ? v : n_dst - 1);
+}
+
+// A19 sampler: one thread per draw i (positive i / k), counter offset + i as k_neg_sample's.
+__global__ __launch_bounds__(256) void k_neg_sample_seg(uint64_t seed, uint64_t offset, const int64_t* __restrict__ src,
+                                                        int64_t n, int k, const int32_t* __restrict__ src_seg,
+                                                        const int32_t* __restrict__ dst_ptr, int n_graphs,
+                                                        int32_t* __restrict__ out) {
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  const uint32_t n_dst = (uint32_t)dst_ptr[n_graphs];
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const uint64_t c = offset + (uint64_t)i;
+    const uint64_t b = c >> 2;
+    const U4 x = philox4x32_10(U4{(uint32_t)b, (uint32_t)(b >> 32), 0u, 0u}, k0, k1);
+    uint32_t lo, cnt;
+    seg_of(src_seg, dst_ptr, n_graphs, src[i / k], lo, cnt);
+    const uint32_t w = (uint32_t)c & 3u;
+    const uint32_t r = w == 0 ? x.x : (w == 1 ? x.y : (w == 2 ? x.z : x.w));
+    out[i] = reduce_seg(r, lo, cnt, n_dst);
+  }
+}
+
 template <int VEC, int G>
 __global__ __launch_bounds__(256) void k_dot_fwd(const int32_t* __restrict__ src, const int32_t* __restrict__ dst,
                                                  int64_t n_pairs, const float* __restrict__ zs, int64_t lds,
@@ -201,14 +238,20 @@ __device__ __forceinline__ float soft_arg(float s, float scale) {
 // be 0: then no Philox block is computed), pairs t = k + 1 .. k + m take destination given[e * m + (t - k - 1)].
 // K takes k's place everywhere else (slots, neg, normalisers, ranks); a batch that straddles the boundary clips its
 // Philox window to its drawn pairs.  Without GIVEN, K = k and given / m are not read.
-template <int VEC, int G, bool ONE, bool RANK, int OBJ, bool GIVEN>
+//
+// A19 (SEG): a draw of positive e lands in the destinations of its source's graph, lo + hi32(word * n) in place of
+// hi32(word * n_dst): one src_seg load and two dst_ptr loads per positive, nothing else differs.  Without SEG
+// src_seg / dst_ptr / n_graphs are not read.
+template <int VEC, int G, bool ONE, bool RANK, int OBJ, bool GIVEN, bool SEG>
 __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ pos, int64_t E, int k, uint64_t seed,
                                                   uint64_t offset, uint32_t n_dst, const float* __restrict__ zs,
                                                   int64_t lds, const float* __restrict__ zd, int64_t ldd, int F,
                                                   float w_pos, float w_neg, float xscale, float* __restrict__ coef,
                                                   int64_t* __restrict__ neg, float* __restrict__ partial,
                                                   int32_t* __restrict__ n_gt, int32_t* __restrict__ n_eq,
-                                                  const int32_t* __restrict__ given, int m) {
+                                                  const int32_t* __restrict__ given, int m,
+                                                  const int32_t* __restrict__ src_seg,
+                                                  const int32_t* __restrict__ dst_ptr, int n_graphs) {
   constexpr bool TWO_PHASE = !RANK && (OBJ == kObjSoftmax || OBJ == kObjSelfAdv);
   constexpr bool POS_IS_SUM = !RANK && (OBJ == kObjSoftmax || OBJ == kObjBpr);
   constexpr int EPW = 64 / G;   // edges per wave
@@ -228,6 +271,8 @@ __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ po
     const int64_t d0 = pos[E + e];
     const int64_t s0 = pos[e];
     const float* a = zs + s0 * lds;
+    uint32_t seg_lo = 0u, seg_n = n_dst;
+    if constexpr (SEG) seg_of(src_seg, dst_ptr, n_graphs, s0, seg_lo, seg_n);
     // pair t's loss term, coefficient and (t >= 1) drawn pair; e = exp(-|s|) serves softplus and sigmoid alike
     auto finish_pair = [&](int t, float s, int64_t idm) {
       const float ex = expf(-fabsf(s));
@@ -347,7 +392,8 @@ __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ po
           const uint64_t c = base + (uint64_t)(t - 1);
           const uint32_t wx = word_of(X, (uint32_t)c & 3u), wy = word_of(Y, (uint32_t)c & 3u);
           const uint32_t r = (c >> 2) == b0 ? wx : wy;
-          id[u] = reduce_range(r, n_dst);
+          if constexpr (SEG) id[u] = reduce_seg(r, seg_lo, seg_n, n_dst);
+          else id[u] = reduce_range(r, n_dst);
         } else if (GIVEN && t > k && t <= K) {
           id[u] = g_cur[u];
         }
@@ -736,11 +782,12 @@ int link_common_checks(const char* what, const int64_t* pos, int64_t E, int64_t 
 }
 
 // GIVEN (A18): k uniform draws + m given destinations per positive (given int32 [E, m]); otherwise m = 0.
-template <bool RANK, int OBJ = kObjBce, bool GIVEN = false>
+template <bool RANK, int OBJ = kObjBce, bool GIVEN = false, bool SEG = false>
 void launch_link_fwd(const LinkShape& sh, hipStream_t s, const int64_t* pos, int64_t E, int k, uint64_t seed,
                      uint64_t offset, uint32_t n_dst, const float* z_src, int64_t ld_src, const float* z_dst,
                      int64_t ld_dst, int F, float* coef, int64_t* neg, float* partial, int32_t* n_gt, int32_t* n_eq,
-                     float param = 0.0f, const int32_t* given = nullptr, int m = 0) {
+                     float param = 0.0f, const int32_t* given = nullptr, int m = 0, const int32_t* src_seg = nullptr,
+                     const int32_t* dst_ptr = nullptr, int n_graphs = 0) {
   const int K = k + m;
   float w_pos = (float)(0.5 / (double)E), w_neg = (float)(0.5 / ((double)E * (double)K)), xscale = 0.0f;
   if (OBJ == kObjSoftmax) {
@@ -753,12 +800,12 @@ void launch_link_fwd(const LinkShape& sh, hipStream_t s, const int64_t* pos, int
     xscale = param;
   }
   constexpr const char* kEpilogue[] = {"LOSS", "SOFTMAX", "BPR", "SELFADV"};
-  HGIN_TRACE("k_link_fwd<%d,%d,%s,%s%s>", sh.vec ? 4 : 1, sh.g, sh.one ? "ONE" : "LOOP",
-             RANK ? "RANK" : kEpilogue[OBJ], GIVEN ? ",GIVEN" : "");
-#define HGIN_LINK_FWD(VEC_, G_, ONE_)                                                                                \
-  k_link_fwd<VEC_, G_, ONE_, RANK, OBJ, GIVEN><<<sh.grid, 256, 0, s>>>(pos, E, k, seed, offset, n_dst, z_src, ld_src, \
-                                                                       z_dst, ld_dst, F, w_pos, w_neg, xscale, coef,  \
-                                                                       neg, partial, n_gt, n_eq, given, m)
+  HGIN_TRACE("k_link_fwd<%d,%d,%s,%s%s%s>", sh.vec ? 4 : 1, sh.g, sh.one ? "ONE" : "LOOP",
+             RANK ? "RANK" : kEpilogue[OBJ], GIVEN ? ",GIVEN" : "", SEG ? ",SEG" : "");
+#define HGIN_LINK_FWD(VEC_, G_, ONE_)                                                                               \
+  k_link_fwd<VEC_, G_, ONE_, RANK, OBJ, GIVEN, SEG><<<sh.grid, 256, 0, s>>>(                                         \
+      pos, E, k, seed, offset, n_dst, z_src, ld_src, z_dst, ld_dst, F, w_pos, w_neg, xscale, coef, neg, partial, n_gt, \
+      n_eq, given, m, src_seg, dst_ptr, n_graphs)
   if (sh.vec) {
     if (!sh.one) HGIN_LINK_FWD(4, 64, false);
     else HGIN_G_SWITCH(sh.g, HGIN_LINK_FWD(4, G, true))
@@ -932,6 +979,122 @@ extern "C" int hgin_link_rank_neg_f32(const int64_t* pos, int64_t n_pos, int64_t
   launch_link_fwd<true, kObjBce, true>(sh, as_stream(stream), pos, n_pos, (int)k, seed, offset, (uint32_t)n_dst, z_src,
                                        ld_src, z_dst, ld_dst, (int)F, nullptr, nullptr, nullptr, n_greater, n_equal,
                                        0.0f, neg_dst, (int)m);
+  return check_launch(what);
+}
+
+// ---- A19 entry points: graph-local draws ----------------------------------------------------------------------------
+namespace {
+
+// m = 0 (then neg_dst may be NULL and k >= 1) or A18's k >= 0, m >= 1 with neg_dst
+int link_seg_checks(const char* what, const int64_t* pos, int64_t E, int64_t k, int64_t n_dst, const int32_t* neg_dst,
+                    int64_t m, const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F,
+                    const int32_t* src_seg, const int32_t* dst_ptr, int64_t n_graphs) {
+  HGIN_ARG_CHECK(m >= 0 && m < (int64_t(1) << 31), "%s: m = %lld must be >= 0", what, (long long)m);
+  const int rc = m == 0 ? link_common_checks(what, pos, E, k, n_dst, z_src, ld_src, z_dst, ld_dst, F)
+                        : link_given_checks(what, pos, E, k, n_dst, neg_dst, m, z_src, ld_src, z_dst, ld_dst, F);
+  if (rc != HGIN_OK) return rc;
+  HGIN_ARG_CHECK(n_graphs >= 1 && n_graphs < (int64_t(1) << 31), "%s: n_graphs = %lld must be in [1, 2^31)", what,
+                 (long long)n_graphs);
+  HGIN_ARG_CHECK(src_seg != nullptr, "%s: src_seg NULL", what);
+  HGIN_ARG_CHECK(dst_ptr != nullptr, "%s: dst_ptr NULL", what);
+  return HGIN_OK;
+}
+
+}  // namespace
+
+extern "C" int hgin_neg_sample_seg(uint64_t seed, uint64_t offset, const int64_t* src, int64_t n_pos, int64_t k,
+                                   const int32_t* src_seg, const int32_t* dst_ptr, int64_t n_graphs, int32_t* out,
+                                   void* stream) {
+  const char* what = "hgin_neg_sample_seg";
+  HGIN_ARG_CHECK(n_pos >= 0 && n_pos < (int64_t(1) << 31), "%s: E = %lld must be in [0, 2^31)", what,
+                 (long long)n_pos);
+  HGIN_ARG_CHECK(k >= 0 && k < (int64_t(1) << 31), "%s: k = %lld must be >= 0", what, (long long)k);
+  HGIN_ARG_CHECK(n_pos * k < (int64_t(1) << 31), "%s: E * k = %lld must be < 2^31", what, (long long)(n_pos * k));
+  HGIN_ARG_CHECK(n_graphs >= 1 && n_graphs < (int64_t(1) << 31), "%s: n_graphs = %lld must be in [1, 2^31)", what,
+                 (long long)n_graphs);
+  if (n_pos * k == 0) return HGIN_OK;
+  HGIN_ARG_CHECK(src != nullptr, "%s: src NULL", what);
+  HGIN_ARG_CHECK(src_seg != nullptr, "%s: src_seg NULL", what);
+  HGIN_ARG_CHECK(dst_ptr != nullptr, "%s: dst_ptr NULL", what);
+  HGIN_ARG_CHECK(out != nullptr, "%s: out NULL", what);
+  const int64_t n = n_pos * k;
+  const int64_t grid = ceil_div(n, 256);
+  HGIN_TRACE("k_neg_sample_seg");
+  k_neg_sample_seg<<<(unsigned)(grid < 65536 ? grid : 65536), 256, 0, as_stream(stream)>>>(
+      seed, offset, src, n, (int)k, src_seg, dst_ptr, (int)n_graphs, out);
+  return check_launch(what);
+}
+
+extern "C" int hgin_link_loss_fwd_seg_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64_t seed, uint64_t offset,
+                                          int64_t n_dst, const int32_t* neg_dst, int64_t m, const float* z_src,
+                                          int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F, float* coef,
+                                          int64_t* neg, float* loss, void* workspace, size_t workspace_bytes,
+                                          int32_t objective, float param, const int32_t* src_seg,
+                                          const int32_t* dst_ptr, int64_t n_graphs, void* stream) {
+  const char* what = "hgin_link_loss_fwd_seg_f32";
+  const int rc = link_seg_checks(what, pos, n_pos, k, n_dst, neg_dst, m, z_src, ld_src, z_dst, ld_dst, F, src_seg,
+                                 dst_ptr, n_graphs);
+  if (rc != HGIN_OK) return rc;
+  HGIN_ARG_CHECK(coef != nullptr, "%s: coef NULL", what);
+  HGIN_ARG_CHECK(neg != nullptr, "%s: neg NULL", what);
+  HGIN_ARG_CHECK(loss != nullptr, "%s: loss NULL", what);
+  HGIN_ARG_CHECK(objective >= kObjBce && objective <= kObjSelfAdv, "%s: objective = %d must be in [0, 3]", what,
+                 (int)objective);
+  HGIN_ARG_CHECK(objective != kObjSoftmax || (std::isfinite(param) && param > 0.0f),
+                 "%s: temperature = %g must be finite and > 0", what, (double)param);
+  HGIN_ARG_CHECK(objective != kObjSelfAdv || (std::isfinite(param) && param >= 0.0f),
+                 "%s: alpha = %g must be finite and >= 0", what, (double)param);
+  if (workspace == nullptr || workspace_bytes < (size_t)kLinkMaxGrid * sizeof(float)) {
+    set_error("%s: workspace %zu bytes < required %zu", what, workspace_bytes, (size_t)kLinkMaxGrid * sizeof(float));
+    return HGIN_E_WORKSPACE;
+  }
+  hipStream_t s = as_stream(stream);
+  const LinkShape sh = link_shape(n_pos, F, z_src, ld_src, z_dst, ld_dst);
+  float* partial = static_cast<float*>(workspace);
+#define HGIN_LINK_SEG(OBJ_, GIVEN_)                                                                                 \
+  launch_link_fwd<false, OBJ_, GIVEN_, true>(sh, s, pos, n_pos, (int)k, seed, offset, (uint32_t)n_dst, z_src, ld_src, \
+                                             z_dst, ld_dst, (int)F, coef, neg, partial, nullptr, nullptr, param,     \
+                                             neg_dst, (int)m, src_seg, dst_ptr, (int)n_graphs)
+#define HGIN_LINK_SEG_OBJ(GIVEN_)                                   \
+  do {                                                              \
+    if (objective == kObjBce) HGIN_LINK_SEG(kObjBce, GIVEN_);       \
+    else if (objective == kObjSoftmax) HGIN_LINK_SEG(kObjSoftmax, GIVEN_); \
+    else if (objective == kObjBpr) HGIN_LINK_SEG(kObjBpr, GIVEN_);  \
+    else HGIN_LINK_SEG(kObjSelfAdv, GIVEN_);                        \
+  } while (0)
+  if (m > 0) HGIN_LINK_SEG_OBJ(true);
+  else HGIN_LINK_SEG_OBJ(false);
+#undef HGIN_LINK_SEG_OBJ
+#undef HGIN_LINK_SEG
+  const int rc2 = check_launch(what);
+  if (rc2 != HGIN_OK) return rc2;
+  HGIN_TRACE("k_link_loss_sum");
+  k_link_loss_sum<<<1, 256, 0, s>>>(partial, (int)sh.grid, loss);
+  return check_launch(what);
+}
+
+extern "C" int hgin_link_rank_seg_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64_t seed, uint64_t offset,
+                                      int64_t n_dst, const int32_t* neg_dst, int64_t m, const float* z_src,
+                                      int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F,
+                                      int32_t* n_greater, int32_t* n_equal, const int32_t* src_seg,
+                                      const int32_t* dst_ptr, int64_t n_graphs, void* stream) {
+  const char* what = "hgin_link_rank_seg_f32";
+  const int rc = link_seg_checks(what, pos, n_pos, k, n_dst, neg_dst, m, z_src, ld_src, z_dst, ld_dst, F, src_seg,
+                                 dst_ptr, n_graphs);
+  if (rc != HGIN_OK) return rc;
+  HGIN_ARG_CHECK(n_greater != nullptr, "%s: n_greater NULL", what);
+  HGIN_ARG_CHECK(n_equal != nullptr, "%s: n_equal NULL", what);
+  const LinkShape sh = link_shape(n_pos, F, z_src, ld_src, z_dst, ld_dst);
+  if (m > 0)
+    launch_link_fwd<true, kObjBce, true, true>(sh, as_stream(stream), pos, n_pos, (int)k, seed, offset, (uint32_t)n_dst,
+                                               z_src, ld_src, z_dst, ld_dst, (int)F, nullptr, nullptr, nullptr,
+                                               n_greater, n_equal, 0.0f, neg_dst, (int)m, src_seg, dst_ptr,
+                                               (int)n_graphs);
+  else
+    launch_link_fwd<true, kObjBce, false, true>(sh, as_stream(stream), pos, n_pos, (int)k, seed, offset,
+                                                (uint32_t)n_dst, z_src, ld_src, z_dst, ld_dst, (int)F, nullptr, nullptr,
+                                                nullptr, n_greater, n_equal, 0.0f, nullptr, 0, src_seg, dst_ptr,
+                                                (int)n_graphs);
   return check_launch(what);
 }
 

@@ -29,22 +29,46 @@ namespace {
 // pair of counters per lane and query block.  blockIdx.x = split * n_qblocks + query block; a split is a contiguous
 // range of destination tiles.  The (tile, K-stage) sequence is one flat pipeline: the next stage's global loads are in
 // flight under this stage's MFMAs, across tile boundaries too.
-template <bool VEC>
+// A19 (SEG): a lane compares a destination only inside its query column's segment [lo, lo + n) (two more registers
+// per column), and the workgroup's splits cut the tiles its 128 queries' segments cover instead of all n_tiles
+// (tiles_per_split / n_tiles are then unused; `splits` is).
+template <bool VEC, bool SEG>
 __global__ __launch_bounds__(256, 2) void k_rank_sweep(const int64_t* __restrict__ pos, int64_t E, int64_t n_src,
                                                     int64_t n_dst, const float* __restrict__ zs, int64_t lds_,
                                                     const float* __restrict__ zd, int64_t ldd, int F,
                                                     const float* __restrict__ thr, int32_t* __restrict__ n_gt,
                                                     int32_t* __restrict__ n_eq, int64_t n_qblocks,
-                                                    int64_t tiles_per_split, int64_t n_tiles) {
+                                                    int64_t tiles_per_split, int64_t n_tiles, int64_t splits,
+                                                    const int32_t* __restrict__ src_seg,
+                                                    const int32_t* __restrict__ dst_ptr, int n_graphs) {
   __shared__ __attribute__((aligned(16))) float As[kRankTile * kRankRow];   // destinations
   __shared__ __attribute__((aligned(16))) float Bs[kRankTile * kRankRow];   // queries
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5, wm = wave >> 1, wn = wave & 1;
   const int64_t qb = (int64_t)blockIdx.x % n_qblocks, split = (int64_t)blockIdx.x / n_qblocks;
   const int64_t q0 = qb * kRankTile;
-  const int64_t t_beg = split * tiles_per_split;
-  const int64_t t_end = t_beg + tiles_per_split < n_tiles ? t_beg + tiles_per_split : n_tiles;
-  if (t_beg >= t_end) return;
+  int64_t t_beg = split * tiles_per_split;
+  int64_t t_end = t_beg + tiles_per_split < n_tiles ? t_beg + tiles_per_split : n_tiles;
+  if constexpr (!SEG)
+    if (t_beg >= t_end) return;
+
+  // this lane's query columns
+  float th[2];
+  uint32_t dq[2], slo[2] = {0u, 0u}, sn[2] = {0u, 0u};
+  int64_t qcol[2];
+  int gt[2] = {0, 0}, eq[2] = {0, 0};
+#pragma unroll
+  for (int tn = 0; tn < 2; ++tn) {
+    qcol[tn] = q0 + wn * 64 + tn * 32 + li;
+    const int64_t q = qcol[tn] < E ? qcol[tn] : E - 1;
+    th[tn] = thr[q];
+    dq[tn] = (uint32_t)pos[E + q];
+    if constexpr (SEG) seg_range(src_seg, dst_ptr, n_graphs, clamp_id(pos[q], n_src), n_dst, slo[tn], sn[tn]);
+  }
+  if constexpr (SEG) {
+    seg_tile_slice(slo, sn, split, splits, t_beg, t_end);
+    if (t_beg >= t_end) return;   // block-uniform
+  }
 
   // staging: thread (r = tid / 8, kq = tid % 8) moves features 4 kq .. 4 kq + 3 of rows r, r + 32, r + 64, r + 96;
   // rows past the end are clamped to the last one (loaded, never counted)
@@ -54,18 +78,6 @@ __global__ __launch_bounds__(256, 2) void k_rank_sweep(const int64_t* __restrict
   for (int i = 0; i < 4; ++i) {
     const int64_t q = q0 + lr + 32 * i < E ? q0 + lr + 32 * i : E - 1;
     qrow[i] = zs + clamp_id(pos[q], n_src) * lds_;
-  }
-  // this lane's query columns
-  float th[2];
-  uint32_t dq[2];
-  int64_t qcol[2];
-  int gt[2] = {0, 0}, eq[2] = {0, 0};
-#pragma unroll
-  for (int tn = 0; tn < 2; ++tn) {
-    qcol[tn] = q0 + wn * 64 + tn * 32 + li;
-    const int64_t q = qcol[tn] < E ? qcol[tn] : E - 1;
-    th[tn] = thr[q];
-    dq[tn] = (uint32_t)pos[E + q];
   }
 
   const int nk = (F + kRankBK - 1) / kRankBK;
@@ -120,7 +132,8 @@ __global__ __launch_bounds__(256, 2) void k_rank_sweep(const int64_t* __restrict
         const bool in = c < (uint32_t)n_dst;
 #pragma unroll
         for (int tn = 0; tn < 2; ++tn) {
-          const bool ok = in && c != dq[tn];
+          bool ok = in && c != dq[tn];
+          if constexpr (SEG) ok = ok && c - slo[tn] < sn[tn];   // unsigned: slo <= c < slo + sn
           const float x = acc[tm][tn][v];
           gt[tn] += (ok && x > th[tn]) ? 1 : 0;
           eq[tn] += (ok && x == th[tn]) ? 1 : 0;
@@ -159,14 +172,19 @@ __device__ __forceinline__ float diag_score(const float* __restrict__ a, const f
   return x;
 }
 
-template <bool VEC, bool FILTER>
+// A19 (SEG, with FILTER): a known neighbour is subtracted only inside the query's segment [lo, lo + n), and
+// n_cand = n - 1 - distinct.
+template <bool VEC, bool FILTER, bool SEG = false>
 __global__ __launch_bounds__(256) void k_rank_pairs(const int64_t* __restrict__ pos, int64_t E, int64_t n_src,
                                                     int64_t n_dst, const float* __restrict__ zs, int64_t lds_,
                                                     const float* __restrict__ zd, int64_t ldd, int F,
                                                     const int32_t* __restrict__ rowptr,
                                                     const int32_t* __restrict__ col, float* __restrict__ thr,
                                                     int32_t* __restrict__ n_gt, int32_t* __restrict__ n_eq,
-                                                    int32_t* __restrict__ n_cand) {
+                                                    int32_t* __restrict__ n_cand,
+                                                    const int32_t* __restrict__ src_seg = nullptr,
+                                                    const int32_t* __restrict__ dst_ptr = nullptr,
+                                                    int n_graphs = 0) {
   const int lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
   const int64_t qbase = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 32;
   if (qbase >= E) return;   // the whole wave
@@ -186,12 +204,15 @@ __global__ __launch_bounds__(256) void k_rank_pairs(const int64_t* __restrict__ 
       deg = rowptr[s + 1] - beg;
     }
     const float th = thr[q];
+    uint32_t slo = 0u, sn = (uint32_t)n_dst;
+    if constexpr (SEG) seg_range(src_seg, dst_ptr, n_graphs, s, n_dst, slo, sn);
     int sub_gt = 0, sub_eq = 0, distinct = 0;
     for (int t = 0; __any(t < deg); ++t) {   // wave-uniform trip count: every lane takes part in every MFMA
       const bool has = t < deg;
       const int64_t c = has ? (int64_t)col[beg + t] : 0;
       const bool dup = has && t > 0 && (int64_t)col[beg + t - 1] == c;   // columns are sorted: duplicates are adjacent
-      const bool ok = has && !dup && c != d && c >= 0 && c < n_dst;
+      bool ok = has && !dup && c != d && c >= 0 && c < n_dst;
+      if constexpr (SEG) ok = ok && (uint32_t)c - slo < sn;
       const float x = diag_score<VEC>(zd + clamp_id(c, n_dst) * ldd, b, F, lh, vsel);
       if (ok) {
         ++distinct;
@@ -202,7 +223,7 @@ __global__ __launch_bounds__(256) void k_rank_pairs(const int64_t* __restrict__ 
     if (owner && valid) {
       n_gt[q] -= sub_gt;
       n_eq[q] -= sub_eq;
-      n_cand[q] = (int32_t)(n_dst - 1 - distinct);
+      n_cand[q] = SEG ? (int32_t)sn - 1 - distinct : (int32_t)(n_dst - 1 - distinct);
     }
   }
 }
@@ -223,12 +244,15 @@ extern "C" int hgin_link_full_rank_workspace_size(int64_t n_pos, int64_t n_dst, 
   return HGIN_OK;
 }
 
-extern "C" int hgin_link_full_rank_f32(const int64_t* pos, int64_t n_pos, int64_t n_src, int64_t n_dst,
-                                       const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst,
-                                       int64_t F, const int32_t* known_rowptr, const int32_t* known_col,
-                                       int32_t* n_greater, int32_t* n_equal, int32_t* n_cand, void* ws,
-                                       size_t ws_bytes, void* stream) {
-  const char* what = "hgin_link_full_rank_f32";
+namespace {
+
+// A15 (src_seg = NULL) and A19 behind one set of checks and launches
+int full_rank_impl(const char* what, const int64_t* pos, int64_t n_pos, int64_t n_src, int64_t n_dst,
+                   const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F,
+                   const int32_t* known_rowptr, const int32_t* known_col, int32_t* n_greater, int32_t* n_equal,
+                   int32_t* n_cand, void* ws, size_t ws_bytes, const int32_t* src_seg, const int32_t* dst_ptr,
+                   int n_graphs, void* stream) {
+  const bool seg = src_seg != nullptr;
   const int64_t E = n_pos;
   HGIN_ARG_CHECK(E >= 1 && E < (int64_t(1) << 31), "%s: E = %lld must be in [1, 2^31)", what, (long long)E);
   HGIN_ARG_CHECK(n_src >= 1 && n_src < (int64_t(1) << 31), "%s: n_src must be in [1, 2^31)", what);
@@ -261,19 +285,52 @@ extern "C" int hgin_link_full_rank_f32(const int64_t* pos, int64_t n_pos, int64_
   rc = memset_async(n_equal, 0, (size_t)E * sizeof(int32_t), s, what);
   if (rc != HGIN_OK) return rc;
   HGIN_TRACE("k_rank_pairs<%d,THR>", vec ? 4 : 1);
-  HGIN_TRACE("k_rank_sweep<%d> splits=%lld", vec ? 4 : 1, (long long)splits);
-  HGIN_TRACE("k_rank_pairs<%d,FILTER>", vec ? 4 : 1);
-#define HGIN_RANK_LAUNCH(VEC_)                                                                                       \
+  HGIN_TRACE("k_rank_sweep<%d%s> splits=%lld", vec ? 4 : 1, seg ? ",SEG" : "", (long long)splits);
+  HGIN_TRACE("k_rank_pairs<%d,FILTER%s>", vec ? 4 : 1, seg ? ",SEG" : "");
+#define HGIN_RANK_LAUNCH(VEC_, SEG_)                                                                                 \
   do {                                                                                                               \
     k_rank_pairs<VEC_, false><<<pair_grid, 256, 0, s>>>(pos, E, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, (int)F,  \
                                                         nullptr, nullptr, thr, nullptr, nullptr, nullptr);           \
-    k_rank_sweep<VEC_><<<sweep_grid, 256, 0, s>>>(pos, E, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, (int)F, thr,   \
-                                                  n_greater, n_equal, n_qblocks, tiles_per_split, n_tiles);          \
-    k_rank_pairs<VEC_, true><<<pair_grid, 256, 0, s>>>(pos, E, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, (int)F,   \
-                                                       known_rowptr, known_col, thr, n_greater, n_equal, n_cand);    \
+    k_rank_sweep<VEC_, SEG_><<<sweep_grid, 256, 0, s>>>(pos, E, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, (int)F,  \
+                                                        thr, n_greater, n_equal, n_qblocks, tiles_per_split,         \
+                                                        n_tiles, splits, src_seg, dst_ptr, n_graphs);                \
+    k_rank_pairs<VEC_, true, SEG_><<<pair_grid, 256, 0, s>>>(pos, E, n_src, n_dst, z_src, ld_src, z_dst, ld_dst,     \
+                                                             (int)F, known_rowptr, known_col, thr, n_greater,        \
+                                                             n_equal, n_cand, src_seg, dst_ptr, n_graphs);           \
   } while (0)
-  if (vec) HGIN_RANK_LAUNCH(true);
-  else HGIN_RANK_LAUNCH(false);
+  if (seg) {
+    if (vec) HGIN_RANK_LAUNCH(true, true);
+    else HGIN_RANK_LAUNCH(false, true);
+  } else {
+    if (vec) HGIN_RANK_LAUNCH(true, false);
+    else HGIN_RANK_LAUNCH(false, false);
+  }
 #undef HGIN_RANK_LAUNCH
   return check_launch(what);
+}
+
+}  // namespace
+
+extern "C" int hgin_link_full_rank_f32(const int64_t* pos, int64_t n_pos, int64_t n_src, int64_t n_dst,
+                                       const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst,
+                                       int64_t F, const int32_t* known_rowptr, const int32_t* known_col,
+                                       int32_t* n_greater, int32_t* n_equal, int32_t* n_cand, void* ws,
+                                       size_t ws_bytes, void* stream) {
+  return full_rank_impl("hgin_link_full_rank_f32", pos, n_pos, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, F,
+                        known_rowptr, known_col, n_greater, n_equal, n_cand, ws, ws_bytes, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int hgin_link_full_rank_seg_f32(const int64_t* pos, int64_t n_pos, int64_t n_src, int64_t n_dst,
+                                           const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst,
+                                           int64_t F, const int32_t* known_rowptr, const int32_t* known_col,
+                                           int32_t* n_greater, int32_t* n_equal, int32_t* n_cand, void* ws,
+                                           size_t ws_bytes, const int32_t* src_seg, const int32_t* dst_ptr,
+                                           int64_t n_graphs, void* stream) {
+  const char* what = "hgin_link_full_rank_seg_f32";
+  HGIN_ARG_CHECK(n_graphs >= 1 && n_graphs < (int64_t(1) << 31), "%s: n_graphs = %lld must be in [1, 2^31)", what,
+                 (long long)n_graphs);
+  HGIN_ARG_CHECK(src_seg != nullptr, "%s: src_seg NULL", what);
+  HGIN_ARG_CHECK(dst_ptr != nullptr, "%s: dst_ptr NULL", what);
+  return full_rank_impl(what, pos, n_pos, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, F, known_rowptr, known_col,
+                        n_greater, n_equal, n_cand, ws, ws_bytes, src_seg, dst_ptr, (int)n_graphs, stream);
 }

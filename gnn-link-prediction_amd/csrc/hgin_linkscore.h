@@ -38,6 +38,46 @@ __device__ __forceinline__ void mfma_k8(f32x16& acc, const float4& a, const floa
   acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
 }
 
+// A19: the destinations [lo, lo + n) of the graph of source row s: g = src_seg[s] clamped into [0, n_graphs),
+// dst_ptr[g] .. dst_ptr[g + 1] kept inside [0, n_dst].
+__device__ __forceinline__ void seg_range(const int32_t* __restrict__ src_seg, const int32_t* __restrict__ dst_ptr,
+                                          int n_graphs, int64_t s, int64_t n_dst, uint32_t& lo, uint32_t& n) {
+  int g = src_seg[s];
+  g = g < 0 ? 0 : (g >= n_graphs ? n_graphs - 1 : g);
+  int64_t a = dst_ptr[g], b = dst_ptr[g + 1];
+  a = a < 0 ? 0 : (a > n_dst ? n_dst : a);
+  b = b < a ? a : (b > n_dst ? n_dst : b);
+  lo = (uint32_t)a;
+  n = (uint32_t)(b - a);
+}
+
+// A19: the destination tiles of this workgroup.  Its query columns' non-empty segments span the tiles
+// [min lo / 128, ceil(max hi / 128)) (block-wide integer min / max through LDS); split `split` of `splits` takes a
+// contiguous slice of them, which may be empty (t_beg >= t_end).  Every thread of the workgroup must call it.
+__device__ __forceinline__ void seg_tile_slice(const uint32_t (&lo)[2], const uint32_t (&n)[2], int64_t split,
+                                               int64_t splits, int64_t& t_beg, int64_t& t_end) {
+  __shared__ int s_lo, s_hi;
+  if (threadIdx.x == 0) {
+    s_lo = 0x7fffffff;
+    s_hi = 0;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int tn = 0; tn < 2; ++tn)
+    if (n[tn] != 0u) {
+      atomicMin(&s_lo, (int)lo[tn]);
+      atomicMax(&s_hi, (int)(lo[tn] + n[tn]));
+    }
+  __syncthreads();
+  const int64_t lo_all = s_lo, hi_all = s_hi;
+  t_beg = t_end = 0;
+  if (hi_all <= lo_all) return;   // every segment of the block is empty
+  const int64_t tile_lo = lo_all / kRankTile, tile_hi = (hi_all + kRankTile - 1) / kRankTile;
+  const int64_t per = (tile_hi - tile_lo + splits - 1) / splits;
+  t_beg = tile_lo + split * per;
+  t_end = t_beg + per < tile_hi ? t_beg + per : tile_hi;
+}
+
 // How a sweep over n_dst destinations is cut for n_query queries: enough contiguous ranges of destination tiles
 // (splits) that query blocks x splits reaches kRankTargetBlocks workgroups, never an empty split.
 struct SweepPlan {

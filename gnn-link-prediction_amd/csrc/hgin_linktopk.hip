@@ -35,37 +35,33 @@ __device__ __forceinline__ float entry_score(const int2* e) { return __int_as_fl
 // Geometry as k_rank_sweep (hgin_linkrank.hip): in an accumulator block lane (li, lh) of wave (wm, wn) holds query
 // column li and the destination rows 8 (v / 4) + 4 lh + v % 4, v < 16.  List of (query q, split, wm, lh):
 // lists + ((q * splits + split) * 4 + 2 wm + lh) * k, its fill count in counts at the same index.
-template <bool VEC>
+// A19 (SEG): the workgroup's splits cut the tiles its queries' segments cover (a workgroup with an empty slice leaves
+// at once: the host zeroed the counts), and the insertion path drops a destination outside its column's segment.
+template <bool VEC, bool SEG>
 __global__ __launch_bounds__(256, 2) void k_topk_sweep(const int64_t* __restrict__ src, int64_t Q, int64_t n_src,
                                                     int64_t n_dst, const float* __restrict__ zs, int64_t lds_,
                                                     const float* __restrict__ zd, int64_t ldd, int F,
                                                     const int32_t* __restrict__ rowptr,
                                                     const int32_t* __restrict__ col, int k, int2* lists,
                                                     int32_t* __restrict__ counts, int64_t n_qblocks,
-                                                    int64_t tiles_per_split, int64_t n_tiles, int64_t splits) {
+                                                    int64_t tiles_per_split, int64_t n_tiles, int64_t splits,
+                                                    const int32_t* __restrict__ src_seg,
+                                                    const int32_t* __restrict__ dst_ptr, int n_graphs) {
   __shared__ __attribute__((aligned(16))) float As[kRankTile * kRankRow];   // destinations
   __shared__ __attribute__((aligned(16))) float Bs[kRankTile * kRankRow];   // queries
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5, wm = wave >> 1, wn = wave & 1;
   const int64_t qb = (int64_t)blockIdx.x % n_qblocks, split = (int64_t)blockIdx.x / n_qblocks;
   const int64_t q0 = qb * kRankTile;
-  const int64_t t_beg = split * tiles_per_split;
-  const int64_t t_end = t_beg + tiles_per_split < n_tiles ? t_beg + tiles_per_split : n_tiles;
-  if (t_beg >= t_end) return;   // never: sweep_plan leaves no empty split
-
-  // staging: thread (r = tid / 8, kq = tid % 8) moves features 4 kq .. 4 kq + 3 of rows r, r + 32, r + 64, r + 96;
-  // rows past the end are clamped to the last one (loaded, never selected)
-  const int lr = tid >> 3, lk = (tid & 7) * 4;
-  const float* qrow[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int64_t q = q0 + lr + 32 * i < Q ? q0 + lr + 32 * i : Q - 1;
-    qrow[i] = zs + clamp_id(src[q], n_src) * lds_;
-  }
+  int64_t t_beg = split * tiles_per_split;
+  int64_t t_end = t_beg + tiles_per_split < n_tiles ? t_beg + tiles_per_split : n_tiles;
+  if constexpr (!SEG)
+    if (t_beg >= t_end) return;   // never: sweep_plan leaves no empty split
   // this lane's query columns: threshold (-inf until the list is full; +inf for a column past Q, which never passes),
   // fill count, and the known row of the source
   float th[2];
   int cnt[2] = {0, 0}, kbeg[2] = {0, 0}, kdeg[2] = {0, 0};
+  uint32_t slo[2] = {0u, 0u}, sn[2] = {0u, 0u};
   int64_t qcol[2];
 #pragma unroll
   for (int tn = 0; tn < 2; ++tn) {
@@ -76,11 +72,31 @@ __global__ __launch_bounds__(256, 2) void k_topk_sweep(const int64_t* __restrict
       kbeg[tn] = rowptr[s];
       kdeg[tn] = rowptr[s + 1] - kbeg[tn];
     }
+    if constexpr (SEG) {
+      if (qcol[tn] < Q) seg_range(src_seg, dst_ptr, n_graphs, clamp_id(src[qcol[tn]], n_src), n_dst, slo[tn], sn[tn]);
+      if (sn[tn] == 0u) th[tn] = INFINITY;   // a graph without destinations: nothing passes, the row stays padded
+    }
+  }
+  if constexpr (SEG) {
+    seg_tile_slice(slo, sn, split, splits, t_beg, t_end);
+    if (t_beg >= t_end) return;   // block-uniform
+  }
+
+  // staging: thread (r = tid / 8, kq = tid % 8) moves features 4 kq .. 4 kq + 3 of rows r, r + 32, r + 64, r + 96;
+  // rows past the end are clamped to the last one (loaded, never selected)
+  const int lr = tid >> 3, lk = (tid & 7) * 4;
+  const float* qrow[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int64_t q = q0 + lr + 32 * i < Q ? q0 + lr + 32 * i : Q - 1;
+    qrow[i] = zs + clamp_id(src[q], n_src) * lds_;
   }
 
   // the cold path of one passing accumulator: candidate c with score x for query column tn
   auto offer = [&](int tn, float x, uint32_t c) {
     if (c >= (uint32_t)n_dst) return;   // a clamped row of the last tile
+    if constexpr (SEG)
+      if (c - slo[tn] >= sn[tn]) return;   // outside the query's graph (unsigned: slo <= c < slo + sn)
     int lo = 0, hi = kdeg[tn];
     while (lo < hi) {   // first known column >= c
       const int mid = (lo + hi) >> 1;
@@ -268,11 +284,14 @@ extern "C" int hgin_link_topk_workspace_size(int64_t n_query, int64_t n_dst, int
   return HGIN_OK;
 }
 
-extern "C" int hgin_link_topk_f32(const int64_t* src, int64_t n_query, int64_t n_src, int64_t n_dst,
-                                  const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F,
-                                  const int32_t* known_rowptr, const int32_t* known_col, int64_t k, int32_t* top_idx,
-                                  float* top_score, void* ws, size_t ws_bytes, void* stream) {
-  const char* what = "hgin_link_topk_f32";
+namespace {
+
+// A16 (src_seg = NULL) and A19 behind one set of checks and launches
+int topk_impl(const char* what, const int64_t* src, int64_t n_query, int64_t n_src, int64_t n_dst, const float* z_src,
+              int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F, const int32_t* known_rowptr,
+              const int32_t* known_col, int64_t k, int32_t* top_idx, float* top_score, void* ws, size_t ws_bytes,
+              const int32_t* src_seg, const int32_t* dst_ptr, int n_graphs, void* stream) {
+  const bool seg = src_seg != nullptr;
   const int64_t Q = n_query;
   HGIN_ARG_CHECK(Q >= 1 && Q < (int64_t(1) << 31), "%s: n_query = %lld must be in [1, 2^31)", what, (long long)Q);
   HGIN_ARG_CHECK(n_src >= 1 && n_src < (int64_t(1) << 31), "%s: n_src must be in [1, 2^31)", what);
@@ -300,16 +319,50 @@ extern "C" int hgin_link_topk_f32(const int64_t* src, int64_t n_query, int64_t n
   const unsigned sweep_grid = (unsigned)(plan.n_qblocks * plan.splits);
   const int L = (int)(4 * plan.splits);   // <= kTopkMaxLists
 
-  HGIN_TRACE("k_topk_sweep<%d> splits=%lld", vec ? 4 : 1, (long long)plan.splits);
+  if (seg) {   // a workgroup whose slice of its graphs' tiles is empty writes no count
+    const int rc = memset_async(counts, 0, topk_counts_bytes(Q, plan.splits), s, what);
+    if (rc != HGIN_OK) return rc;
+  }
+  HGIN_TRACE("k_topk_sweep<%d%s> splits=%lld", vec ? 4 : 1, seg ? ",SEG" : "", (long long)plan.splits);
   HGIN_TRACE("k_topk_merge");
-  if (vec)
-    k_topk_sweep<true><<<sweep_grid, 256, 0, s>>>(src, Q, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, (int)F,
-                                                  known_rowptr, known_col, (int)k, lists, counts, plan.n_qblocks,
-                                                  plan.tiles_per_split, plan.n_tiles, plan.splits);
-  else
-    k_topk_sweep<false><<<sweep_grid, 256, 0, s>>>(src, Q, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, (int)F,
-                                                   known_rowptr, known_col, (int)k, lists, counts, plan.n_qblocks,
-                                                   plan.tiles_per_split, plan.n_tiles, plan.splits);
+#define HGIN_TOPK_SWEEP(VEC_, SEG_)                                                                                 \
+  k_topk_sweep<VEC_, SEG_><<<sweep_grid, 256, 0, s>>>(src, Q, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, (int)F,   \
+                                                      known_rowptr, known_col, (int)k, lists, counts,               \
+                                                      plan.n_qblocks, plan.tiles_per_split, plan.n_tiles,           \
+                                                      plan.splits, src_seg, dst_ptr, n_graphs)
+  if (seg) {
+    if (vec) HGIN_TOPK_SWEEP(true, true);
+    else HGIN_TOPK_SWEEP(false, true);
+  } else {
+    if (vec) HGIN_TOPK_SWEEP(true, false);
+    else HGIN_TOPK_SWEEP(false, false);
+  }
+#undef HGIN_TOPK_SWEEP
   k_topk_merge<<<(unsigned)Q, 64, 0, s>>>(lists, counts, L, (int)k, top_idx, top_score);
   return check_launch(what);
+}
+
+}  // namespace
+
+extern "C" int hgin_link_topk_f32(const int64_t* src, int64_t n_query, int64_t n_src, int64_t n_dst,
+                                  const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F,
+                                  const int32_t* known_rowptr, const int32_t* known_col, int64_t k, int32_t* top_idx,
+                                  float* top_score, void* ws, size_t ws_bytes, void* stream) {
+  return topk_impl("hgin_link_topk_f32", src, n_query, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, F, known_rowptr,
+                   known_col, k, top_idx, top_score, ws, ws_bytes, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int hgin_link_topk_seg_f32(const int64_t* src, int64_t n_query, int64_t n_src, int64_t n_dst,
+                                      const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst,
+                                      int64_t F, const int32_t* known_rowptr, const int32_t* known_col, int64_t k,
+                                      int32_t* top_idx, float* top_score, void* ws, size_t ws_bytes,
+                                      const int32_t* src_seg, const int32_t* dst_ptr, int64_t n_graphs,
+                                      void* stream) {
+  const char* what = "hgin_link_topk_seg_f32";
+  HGIN_ARG_CHECK(n_graphs >= 1 && n_graphs < (int64_t(1) << 31), "%s: n_graphs = %lld must be in [1, 2^31)", what,
+                 (long long)n_graphs);
+  HGIN_ARG_CHECK(src_seg != nullptr, "%s: src_seg NULL", what);
+  HGIN_ARG_CHECK(dst_ptr != nullptr, "%s: dst_ptr NULL", what);
+  return topk_impl(what, src, n_query, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, F, known_rowptr, known_col, k,
+                   top_idx, top_score, ws, ws_bytes, src_seg, dst_ptr, (int)n_graphs, stream);
 }

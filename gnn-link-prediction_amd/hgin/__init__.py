@@ -8,7 +8,7 @@ in include/hgin.h).  See DESIGN.md.
 from . import data  # noqa: F401
 from ._lib import HginError, HginUnavailable, build  # noqa: F401
 from .conv import GINConv, GINLayer, HeteroConv, MessagePassing, reset  # noqa: F401
-from .linkpred import (LINK_OBJECTIVES, LinkPredictor, hard_negatives, link_full_metrics, link_full_ranks,  # noqa: F401
+from .linkpred import (LINK_OBJECTIVES, LinkPredictor, LinkSegments, hard_negatives, hard_negatives_seg, link_full_metrics, link_full_ranks,  # noqa: F401
                        link_metrics, link_ranks, link_topk, sampled_link_loss)
 from .models import HetroGAT, HetroGIN  # noqa: F401
 from .qt import QTBaseline  # noqa: F401
@@ -16,4 +16,5 @@ from .train import link_train_step  # noqa: F401
 
 __all__ = ["HetroGIN", "HetroGAT", "QTBaseline", "GINLayer", "GINConv", "HeteroConv", "MessagePassing", "reset", "build",
            "HginError", "HginUnavailable", "data", "LinkPredictor", "sampled_link_loss", "link_ranks", "link_metrics",
-           "link_full_ranks", "link_full_metrics", "link_topk", "link_train_step", "LINK_OBJECTIVES", "hard_negatives"]
+           "link_full_ranks", "link_full_metrics", "link_topk", "link_train_step", "LINK_OBJECTIVES", "hard_negatives",
+           "LinkSegments", "hard_negatives_seg"]

@@ -28,11 +28,17 @@ every query source, known edges left out, from the same sweep with a selecting e
 Given negatives (A18, not in the reference): ``negative_edges`` / ``link_loss`` / ``sampled_link_loss`` / ``link_ranks``
 / ``link_metrics`` take ``neg_dst`` = an integer [E, m] tensor of destinations that join each positive's k uniform draws
 (k may then be 0); ``hard_negatives`` mines such a set with ``link_topk``, ``LinkPredictor(hard=m)`` trains on it.
+
+Batches of graphs (A19, not in the reference): ``LinkSegments`` records which graph of a collated batch every source /
+destination row belongs to; the functions above take it as ``segments=`` (mining: ``hard_negatives_seg``) and then draw
+a negative from the positive's own graph and rank / retrieve among that graph's destinations only;
+``LinkPredictor(graph_local=True)`` builds it from ``graph.batch``.  Without it nothing changes.
 """
 from __future__ import annotations
 
 import ctypes
 import math
+import weakref
 
 import torch
 from torch import Tensor
@@ -94,23 +100,155 @@ def _given_negatives(what: str, neg_dst: Tensor, n_dst: int) -> Tensor:
     return out
 
 
+# ---------------------------------------------------------------------------------------------------
+# A19: graph-local negatives and candidates (NOT IN REFERENCE)
+# ---------------------------------------------------------------------------------------------------
+class LinkSegments:
+    """Which graph of a collated batch every row of a relation's two node types belongs to (include/hgin.h A19).
+
+    ``batch_src`` integer [n_src]: the graph id of every source row, in any order; ``batch_dst`` integer [n_dst]: the
+    graph id of every destination row, non-decreasing (each graph's destinations form one contiguous block, which is
+    what ``hgin.data.collate`` produces).  Keeps ``src_seg`` (int32 [n_src]), ``dst_ptr`` (int32 [G + 1], dst_ptr[0]
+    = 0, dst_ptr[G] = n_dst) and ``n_graphs`` = G (default: the largest id + 1).  Graphs without rows are allowed on
+    either side.  Validated once, here, with one host sync: ValueError for an unsorted ``batch_dst`` or G < 1,
+    IndexError for an id outside [0, G).
+
+    Passed as ``segments=`` to the link functions, a negative is drawn from the positive's own graph and ranking /
+    top-K see only that graph's destinations."""
+
+    def __init__(self, batch_src: Tensor, batch_dst: Tensor, n_graphs: int = None):
+        what = "LinkSegments"
+        for name, b in (("batch_src", batch_src), ("batch_dst", batch_dst)):
+            if not isinstance(b, Tensor) or b.dtype not in (torch.int32, torch.int64):
+                got = b.dtype if isinstance(b, Tensor) else type(b).__name__
+                raise TypeError(f"{what}: {name} must be an int32 or int64 tensor, got {got}")
+            if b.dim() != 1:
+                raise ValueError(f"{what}: {name} must be one-dimensional, got {tuple(b.shape)}")
+        if batch_src.device != batch_dst.device:
+            raise ValueError(f"{what}: batch_src is on {batch_src.device}, batch_dst on {batch_dst.device}")
+        n_src, n_dst = int(batch_src.numel()), int(batch_dst.numel())
+        if n_src >= 2**31 or n_dst >= 2**31:
+            raise ValueError(f"{what}: more than 2^31 rows")
+        dev = batch_dst.device
+        both = torch.cat([batch_src.reshape(-1).long(), batch_dst.reshape(-1).long()])
+        if both.numel():
+            unsorted = (batch_dst[1:] < batch_dst[:-1]).any().long() if n_dst > 1 else \
+                torch.zeros((), dtype=torch.long, device=dev)
+            lo, hi, unsorted = torch.stack([both.amin(), both.amax(), unsorted]).tolist()   # the one host sync
+        else:
+            lo, hi, unsorted = 0, -1, 0
+        if unsorted:
+            raise ValueError(f"{what}: batch_dst must be non-decreasing (each graph's destinations one contiguous block)")
+        G = int(hi) + 1 if n_graphs is None else int(n_graphs)
+        if n_graphs is None and G < 1:
+            G = 1
+        if G < 1 or G >= 2**31:
+            raise ValueError(f"{what}: n_graphs = {G} must be in [1, 2^31)")
+        if lo < 0 or hi >= G:
+            raise IndexError(f"{what}: graph id out of range [0, {G})")
+        self.n_graphs, self.n_src, self.n_dst = G, n_src, n_dst
+        self.src_seg = batch_src.to(torch.int32).contiguous()
+        ptr = torch.zeros(G + 1, dtype=torch.int64, device=dev)
+        ptr[1:] = torch.cumsum(torch.bincount(batch_dst.long(), minlength=G), 0)
+        self.dst_ptr = ptr.to(torch.int32)
+
+    @classmethod
+    def of(cls, graph, relation) -> "LinkSegments":
+        """The segmentation of ``relation`` = (src_type, name, dst_type) in a collated ``HeteroGraph``, from
+        ``graph.batch``.  A ``PaddedBatch`` is refused: its padding rows carry the id ``cap_graphs``."""
+        from .store import PaddedBatch
+        if isinstance(graph, PaddedBatch):
+            raise ValueError("LinkSegments.of: a PaddedBatch is not supported (its padding rows carry the graph id "
+                             "cap_graphs, past every real graph); collate the graphs with hgin.data.collate instead")
+        relation = tuple(relation)
+        return cls(graph.batch[relation[0]], graph.batch[relation[2]])
+
+    @property
+    def device(self):
+        return self.src_seg.device
+
+
+def _check_segments(what: str, segments, n_src: int, n_dst: int, pos: Tensor = None) -> None:
+    """``segments`` fits the embeddings' row counts, and (with ``pos``) every positive's source is a row of the
+    segmentation and its destination lies in its source's graph: ValueError (IndexError for a source out of range).
+    The positives' check costs one host sync, cached per (pos tensor version, segments) the way ``_known_csr`` caches.
+    Runs on whatever device the tensors live on, so it is reached before a device is needed."""
+    if not isinstance(segments, LinkSegments):
+        raise TypeError(f"{what}: segments must be a LinkSegments, got {type(segments).__name__}")
+    if n_src is not None and int(n_src) != segments.n_src:
+        raise ValueError(f"{what}: segments cover {segments.n_src} source rows, z_src has {int(n_src)}")
+    if int(n_dst) != segments.n_dst:
+        raise ValueError(f"{what}: segments cover {segments.n_dst} destination rows, expected {int(n_dst)}")
+    if pos is None:
+        return
+    ops.check_edge_index(pos)
+    if pos.device != segments.device:
+        raise ValueError(f"{what}: pos is on {pos.device}, segments on {segments.device}")
+    cache = getattr(pos, "_hgin_seg_ok", None)
+    ver = pos._version
+    if cache is not None and cache[0] == ver and segments in cache[1]:
+        return
+    if pos.size(1):
+        if segments.n_src == 0:
+            raise IndexError(f"{what}: pos src index out of range [0, 0)")
+        s, d = pos[0], pos[1]
+        oob = (s < 0) | (s >= segments.n_src)
+        g = segments.src_seg[s.clamp(0, segments.n_src - 1)].long()
+        ptr = segments.dst_ptr.long()
+        leaves = (d < ptr[g]) | (d >= ptr[g + 1])
+        oob, leaves = torch.stack([oob.any(), leaves.any()]).tolist()   # the one host sync
+        if oob:
+            raise IndexError(f"{what}: pos src index out of range [0, {segments.n_src})")
+        if leaves:
+            raise ValueError(f"{what}: a positive's destination lies outside its source's graph")
+    if cache is None or cache[0] != ver:
+        cache = (ver, weakref.WeakSet())
+    cache[1].add(segments)
+    try:
+        pos._hgin_seg_ok = cache
+    except (AttributeError, RuntimeError):
+        pass
+
+
+def _sample_seg(src: Tensor, k: int, seed: int, offset: int, segments: LinkSegments) -> Tensor:
+    """int32 [E * k]: draw i belongs to positive i // k (source ``src[i // k]``) and has Philox counter offset + i,
+    drawn from that source's graph (include/hgin.h A19)."""
+    E, k = int(src.numel()), int(k)
+    out = torch.empty(E * k, dtype=torch.int32, device=src.device)
+    if E * k:
+        _lib.call("hgin_neg_sample_seg", int(seed) & (2**64 - 1), int(offset) & (2**64 - 1), ops._p(src.contiguous()),
+                  E, k, ops._p(segments.src_seg), ops._p(segments.dst_ptr), segments.n_graphs, ops._p(out),
+                  ops._stream(out))
+    return out
+
+
 def negative_edges(edge_index: Tensor, n_dst: int, k: int, seed: int, offset: int = 0,
-                   neg_dst: Tensor = None) -> Tensor:
+                   neg_dst: Tensor = None, segments: LinkSegments = None) -> Tensor:
     """k corrupted copies of every positive edge: src kept, dst drawn uniformly.  With ``neg_dst``
     (integer [E, m]; include/hgin.h A18) every positive gets k + m copies, destinations [k drawn | m given]; k may be
-    0."""
+    0.  With ``segments`` (a ``LinkSegments``; A19) every draw comes from its positive's own graph."""
     m = _given_shape("negative_edges", neg_dst, edge_index)
+    if segments is not None:
+        _check_segments("negative_edges", segments, None, n_dst, edge_index)
     ops.require_device(edge_index, what="negative_edges")
     E = int(edge_index.size(1))
+
+    def draw(n_per):
+        if segments is None:
+            return sample_negative_dst(E * n_per, n_dst, seed, offset, edge_index.device)
+        if n_per < 0 or E * n_per >= 2**31:
+            raise ValueError(f"negative_edges: need k >= 0 and E * k < 2^31 (E = {E}, k = {n_per})")
+        return _sample_seg(edge_index[0], n_per, seed, offset, segments)
+
     if m == 0:
-        dst = sample_negative_dst(E * k, n_dst, seed, offset, edge_index.device).long()
+        dst = draw(int(k)).long()
         src = edge_index[0].repeat_interleave(k)
         return torch.stack([src, dst])
     k = int(k)
     if k < 0 or E * (k + m) >= 2**31:
         raise ValueError(f"negative_edges: need k >= 0 and E * (k + m) < 2^31 (E = {E}, k = {k}, m = {m})")
     given = _given_negatives("negative_edges", neg_dst, n_dst)
-    drawn = sample_negative_dst(E * k, n_dst, seed, offset, edge_index.device).view(E, k)
+    drawn = draw(k).view(E, k)
     dst = torch.cat([drawn, given], 1).reshape(-1).long()
     return torch.stack([edge_index[0].repeat_interleave(k + m), dst])
 
@@ -180,14 +318,20 @@ def _objective(what: str, objective, temperature, alpha):
 
 
 def link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0, objective: str = "bce",
-              temperature: float = 1.0, alpha: float = 1.0, neg_dst: Tensor = None) -> Tensor:
+              temperature: float = 1.0, alpha: float = 1.0, neg_dst: Tensor = None,
+              segments: LinkSegments = None) -> Tensor:
     """The unfused sampled link loss over positives and k uniform negatives per positive: ``objective`` "bce"
     (BCE-with-logits, the default), "softmax", "bpr" or "selfadv" (include/hgin.h A17), as torch ops on the two
-    ``dot_decode`` score vectors.  ``neg_dst`` (integer [E, m]) adds m given negatives per positive (A18)."""
+    ``dot_decode`` score vectors.  ``neg_dst`` (integer [E, m]) adds m given negatives per positive (A18);
+    ``segments`` (a ``LinkSegments``) draws every negative from its positive's own graph (A19)."""
     code, param = _objective("link_loss", objective, temperature, alpha)
     m = _given_shape("link_loss", neg_dst, pos)
-    neg = negative_edges(pos, z_dst.size(0), k, seed, offset) if m == 0 else \
-        negative_edges(pos, z_dst.size(0), k, seed, offset, neg_dst)
+    if segments is not None:
+        _check_segments("link_loss", segments, z_src.size(0), z_dst.size(0), pos)
+        neg = negative_edges(pos, z_dst.size(0), k, seed, offset, neg_dst, segments=segments)
+    else:
+        neg = negative_edges(pos, z_dst.size(0), k, seed, offset) if m == 0 else \
+            negative_edges(pos, z_dst.size(0), k, seed, offset, neg_dst)
     k = int(k) + m
     s_pos = dot_decode(z_src, z_dst, pos)
     s_neg = dot_decode(z_src, z_dst, neg)
@@ -208,12 +352,16 @@ def link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offs
 # ---------------------------------------------------------------------------------------------------
 # A13 / A14: the fused sampled link loss, sampled ranks and the training head (NOT IN REFERENCE)
 # ---------------------------------------------------------------------------------------------------
-def _link_operands(what: str, z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, neg_dst: Tensor = None):
+def _link_operands(what: str, z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, neg_dst: Tensor = None,
+                   segments: LinkSegments = None):
     """Checked operands of the fused kernels: fp32 row-major embeddings of one width, validated positives; with
-    ``neg_dst`` the checked int32 [E, m] set comes back as a seventh item (and k may be 0)."""
+    ``neg_dst`` the checked int32 [E, m] set comes back as a seventh item (and k may be 0).  ``segments`` is checked
+    against the row counts and the positives (``_check_segments``)."""
     m = _given_shape(what, neg_dst, pos)
     if int(k) < (0 if m else 1):
         raise ValueError(f"{what}: need E >= 1, k >= {0 if m else 1} and E * k < 2^31 (k = {int(k)})")
+    if segments is not None:
+        _check_segments(what, segments, z_src.size(0) if z_src.dim() else -1, z_dst.size(0) if z_dst.dim() else -1, pos)
     ops.require_device(z_src, z_dst, pos, neg_dst, what=what)
     for name, z in (("z_src", z_src), ("z_dst", z_dst)):
         if z.dtype != torch.float32:
@@ -250,7 +398,7 @@ def _side_stream(device) -> "torch.cuda.Stream":
 class _SampledLinkLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z_src, z_dst, pos, graph: ops.RelationGraph, k: int, seed: int, offset: int, objective: int = 0,
-                param: float = 0.0, neg_dst: Tensor = None):
+                param: float = 0.0, neg_dst: Tensor = None, segments: LinkSegments = None):
         E, F, dev = int(pos.size(1)), int(z_src.size(1)), z_src.device
         m = 0 if neg_dst is None else int(neg_dst.size(1))   # A18: k uniform + m given negatives per positive
         K = k + m
@@ -260,7 +408,13 @@ class _SampledLinkLossFn(torch.autograd.Function):
         nbytes = ctypes.c_size_t(0)
         _lib.check(_lib.lib().hgin_link_loss_workspace_size(E, ctypes.byref(nbytes)), "hgin_link_loss_workspace_size")
         ws = ops._workspace(nbytes.value, dev)
-        if m:   # the same coef / neg layout with K in place of k: the backward below does not know the difference
+        if segments is not None:   # A19: graph-local draws, given negatives or not; coef / neg as below
+            _lib.call("hgin_link_loss_fwd_seg_f32", ops._p(pos), E, k, int(seed) & (2**64 - 1),
+                      int(offset) & (2**64 - 1), int(z_dst.size(0)), ops._p(neg_dst), m, ops._p(z_src), z_src.stride(0),
+                      ops._p(z_dst), z_dst.stride(0), F, ops._p(coef), ops._p(neg), ops._p(loss), ops._p(ws),
+                      nbytes.value, objective, param, ops._p(segments.src_seg), ops._p(segments.dst_ptr),
+                      segments.n_graphs, ops._stream(loss))
+        elif m:   # the same coef / neg layout with K in place of k: the backward below does not know the difference
             _lib.call("hgin_link_loss_fwd_neg_f32", ops._p(pos), E, k, int(seed) & (2**64 - 1),
                       int(offset) & (2**64 - 1), int(z_dst.size(0)), ops._p(neg_dst), m, ops._p(z_src), z_src.stride(0),
                       ops._p(z_dst), z_dst.stride(0), F, ops._p(coef), ops._p(neg), ops._p(loss), ops._p(ws),
@@ -321,12 +475,12 @@ class _SampledLinkLossFn(torch.autograd.Function):
             _lib.call("hgin_link_loss_bwd_dst_f32", ops._p(csr.rowptr), ops._p(csr.col), ops._p(csr.perm),
                       ops._p(nrow), ops._p(ncol), ops._p(nperm), n_dst, E, ops._p(g), ops._p(coef), ops._p(z_src),
                       z_src.stride(0), F, ops._p(g_dst), g_dst.stride(0), ops._stream(g))
-        return g_src, g_dst, None, None, None, None, None, None, None, None
+        return g_src, g_dst, None, None, None, None, None, None, None, None, None
 
 
 def sampled_link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0,
                       objective: str = "bce", temperature: float = 1.0, alpha: float = 1.0,
-                      neg_dst: Tensor = None) -> Tensor:
+                      neg_dst: Tensor = None, segments: LinkSegments = None) -> Tensor:
     """``link_loss`` in fused form (include/hgin.h A13 / A17): the same pairs (``negative_edges(pos, n_dst, k, seed,
     offset)``) and the same loss, one forward pass that draws the negatives in the kernel and reads every source
     row once, and a deterministic store-and-sum backward (static CSC / CSR of ``pos`` + one sort of the step's
@@ -335,9 +489,16 @@ def sampled_link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: i
     softmax(``alpha`` * score)); only the forward epilogue differs.  ``neg_dst`` (int32 or int64 [E, m] on the device,
     values in [0, n_dst): checked once per tensor version, one host sync) adds m given negatives after each
     positive's k drawn ones (include/hgin.h A18): K = k + m takes k's place in every weight and normaliser, k may be
-    0, and a given destination contributes exactly what the same destination would as a draw.  Returns a scalar; fp32
-    embeddings only."""
+    0, and a given destination contributes exactly what the same destination would as a draw.  ``segments`` (a
+    ``LinkSegments``; include/hgin.h A19) draws every negative from its positive's own graph, at the same Philox
+    counters; with one graph the result is bit for bit the unsegmented one.  Returns a scalar; fp32 embeddings only."""
     code, param = _objective("sampled_link_loss", objective, temperature, alpha)
+    if segments is not None:
+        ops_ = _link_operands("sampled_link_loss", z_src, z_dst, pos, k, neg_dst, segments)
+        z_src, z_dst, pos, graph, _, k = ops_[:6]
+        given = ops_[6] if len(ops_) > 6 else None
+        return _SampledLinkLossFn.apply(z_src, z_dst, pos, graph, k, int(seed), int(offset), code, param, given,
+                                        segments)
     if neg_dst is None:
         z_src, z_dst, pos, graph, _, k = _link_operands("sampled_link_loss", z_src, z_dst, pos, k)
         return _SampledLinkLossFn.apply(z_src, z_dst, pos, graph, k, int(seed), int(offset), code, param)
@@ -345,19 +506,26 @@ def sampled_link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: i
     return _SampledLinkLossFn.apply(z_src, z_dst, pos, graph, k, int(seed), int(offset), code, param, given)
 
 
-def link_ranks(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0, neg_dst: Tensor = None):
+def link_ranks(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0, neg_dst: Tensor = None,
+               segments: LinkSegments = None):
     """(n_greater, n_equal), int32 [E]: how many of each positive's k sampled negatives (the draws of
     ``sampled_link_loss``) score above / exactly equal to it (include/hgin.h A14); with ``neg_dst`` (integer [E, m],
-    e.g. a fixed evaluation set; A18) the counts cover the k draws and the m given negatives, and k may be 0.  No
-    gradient."""
+    e.g. a fixed evaluation set; A18) the counts cover the k draws and the m given negatives, and k may be 0.  With
+    ``segments`` (a ``LinkSegments``; A19) the draws come from each positive's own graph.  No gradient."""
     given = None
     if neg_dst is None:
-        z_src, z_dst, pos, _, E, k = _link_operands("link_ranks", z_src, z_dst, pos, k)
+        z_src, z_dst, pos, _, E, k = _link_operands("link_ranks", z_src, z_dst, pos, k, None, segments)
     else:
-        z_src, z_dst, pos, _, E, k, given = _link_operands("link_ranks", z_src, z_dst, pos, k, neg_dst)
+        z_src, z_dst, pos, _, E, k, given = _link_operands("link_ranks", z_src, z_dst, pos, k, neg_dst, segments)
     z_src, z_dst = z_src.detach(), z_dst.detach()
     n_gt = torch.empty(E, dtype=torch.int32, device=z_src.device)
     n_eq = torch.empty(E, dtype=torch.int32, device=z_src.device)
+    if segments is not None:
+        _lib.call("hgin_link_rank_seg_f32", ops._p(pos), E, k, int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
+                  int(z_dst.size(0)), ops._p(given), 0 if given is None else int(given.size(1)), ops._p(z_src),
+                  z_src.stride(0), ops._p(z_dst), z_dst.stride(0), int(z_src.size(1)), ops._p(n_gt), ops._p(n_eq),
+                  ops._p(segments.src_seg), ops._p(segments.dst_ptr), segments.n_graphs, ops._stream(n_gt))
+        return n_gt, n_eq
     if given is not None:
         _lib.call("hgin_link_rank_neg_f32", ops._p(pos), E, k, int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
                   int(z_dst.size(0)), ops._p(given), int(given.size(1)), ops._p(z_src), z_src.stride(0), ops._p(z_dst),
@@ -383,11 +551,14 @@ def metrics_from_ranks(n_greater: Tensor, n_equal: Tensor, k: int) -> dict:
 
 
 def link_metrics(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0,
-                 neg_dst: Tensor = None) -> dict:
+                 neg_dst: Tensor = None, segments: LinkSegments = None) -> dict:
     """auc / mrr / hits@1 / hits@3 / hits@10 of the positives against k sampled negatives each, as device scalars
     (float64): the ranking kernel + a few reductions over [E]; no host sync before the caller reads a value.  With
     ``neg_dst`` (integer [E, m]; A18) against the k draws and the m given negatives (the set's one-off range check
-    aside)."""
+    aside).  ``segments`` (a ``LinkSegments``; A19): the draws come from each positive's own graph."""
+    if segments is not None:
+        n_gt, n_eq = link_ranks(z_src, z_dst, pos, k, seed, offset, neg_dst, segments=segments)
+        return metrics_from_ranks(n_gt, n_eq, int(k) + (0 if neg_dst is None else int(neg_dst.size(1))))
     if neg_dst is None:
         n_gt, n_eq = link_ranks(z_src, z_dst, pos, k, seed, offset)
         return metrics_from_ranks(n_gt, n_eq, k)
@@ -433,12 +604,18 @@ def _known_csr(known: Tensor, n_src: int, n_dst: int):
     return out
 
 
-def link_full_ranks(z_src: Tensor, z_dst: Tensor, pos: Tensor, known: Tensor = None):
+def link_full_ranks(z_src: Tensor, z_dst: Tensor, pos: Tensor, known: Tensor = None, segments: LinkSegments = None):
     """(n_greater, n_equal, n_cand), int32 [E] (include/hgin.h A15): every positive (s, d) of ``pos`` is ranked against
     every destination c != d, minus the c with (s, c) in ``known`` (an edge index [2, M]; None: unfiltered).
     n_greater / n_equal count the candidates scoring above / exactly equal to the positive, n_cand the candidates.
-    Scores are fp32 dot products on the matrix cores and are never written.  No gradient."""
+    Scores are fp32 dot products on the matrix cores and are never written.  With ``segments`` (a ``LinkSegments``;
+    include/hgin.h A19) the candidates of (s, d) are only the destinations of s's own graph (known edges that leave
+    the graph are never candidates and are not subtracted), and a block of 128 queries sweeps only the destination
+    tiles its graphs cover: sort the positives by graph to visit n_dst / G instead of n_dst.  No gradient."""
     what = "link_full_ranks"
+    if segments is not None:
+        _check_segments(what, segments, z_src.size(0) if z_src.dim() else -1, z_dst.size(0) if z_dst.dim() else -1,
+                        pos if isinstance(pos, Tensor) and pos.dim() == 2 and pos.dtype == torch.long else None)
     ops.require_device(known, what=what)
     z_src, z_dst, pos, _, E, _ = _link_operands(what, z_src, z_dst, pos, 1)
     z_src, z_dst = z_src.detach(), z_dst.detach()
@@ -456,6 +633,12 @@ def link_full_ranks(z_src: Tensor, z_dst: Tensor, pos: Tensor, known: Tensor = N
     _lib.check(_lib.lib().hgin_link_full_rank_workspace_size(E, n_dst, F, ctypes.byref(nbytes)),
                "hgin_link_full_rank_workspace_size")
     ws = ops._workspace(nbytes.value, dev)
+    if segments is not None:
+        _lib.call("hgin_link_full_rank_seg_f32", ops._p(pos), E, n_src, n_dst, ops._p(z_src), z_src.stride(0),
+                  ops._p(z_dst), z_dst.stride(0), F, ops._p(rowptr), ops._p(col), ops._p(n_gt), ops._p(n_eq),
+                  ops._p(n_cand), ops._p(ws), nbytes.value, ops._p(segments.src_seg), ops._p(segments.dst_ptr),
+                  segments.n_graphs, ops._stream(n_gt))
+        return n_gt, n_eq, n_cand
     _lib.call("hgin_link_full_rank_f32", ops._p(pos), E, n_src, n_dst, ops._p(z_src), z_src.stride(0), ops._p(z_dst),
               z_dst.stride(0), F, ops._p(rowptr), ops._p(col), ops._p(n_gt), ops._p(n_eq), ops._p(n_cand), ops._p(ws),
               nbytes.value, ops._stream(n_gt))
@@ -478,9 +661,13 @@ def full_metrics_from_ranks(n_greater: Tensor, n_equal: Tensor, n_cand: Tensor) 
     return out
 
 
-def link_full_metrics(z_src: Tensor, z_dst: Tensor, pos: Tensor, known: Tensor = None) -> dict:
+def link_full_metrics(z_src: Tensor, z_dst: Tensor, pos: Tensor, known: Tensor = None,
+                      segments: LinkSegments = None) -> dict:
     """auc / mrr / hits@1 / hits@3 / hits@10 of the positives against every (filtered) destination, as float64
-    device scalars: ``link_full_ranks`` + a few reductions over [E]; no host sync before the caller reads a value."""
+    device scalars: ``link_full_ranks`` + a few reductions over [E]; no host sync before the caller reads a value.
+    ``segments`` (a ``LinkSegments``; A19): against the destinations of each positive's own graph."""
+    if segments is not None:
+        return full_metrics_from_ranks(*link_full_ranks(z_src, z_dst, pos, known, segments=segments))
     return full_metrics_from_ranks(*link_full_ranks(z_src, z_dst, pos, known))
 
 
@@ -490,12 +677,14 @@ def link_full_metrics(z_src: Tensor, z_dst: Tensor, pos: Tensor, known: Tensor =
 TOPK_MAX = 128
 
 
-def link_topk(z_src: Tensor, z_dst: Tensor, src: Tensor, k: int, known: Tensor = None):
+def link_topk(z_src: Tensor, z_dst: Tensor, src: Tensor, k: int, known: Tensor = None, segments: LinkSegments = None):
     """(idx int32 [Q, k], score float32 [Q, k]) (include/hgin.h A16): for every source ``src[q]`` (int64 [Q], repeats
     allowed) the k best destinations c by <z_src[src[q]], z_dst[c]>, minus the c with (src[q], c) in ``known`` (an
     edge index [2, M]; None: unfiltered), ordered by (score descending, index ascending); rows with fewer than k
     candidates are padded with idx -1 / score -inf.  The scores are the bits ``link_full_ranks`` compares; no
-    [Q, n_dst] score matrix exists.  1 <= k <= 128.  No gradient."""
+    [Q, n_dst] score matrix exists.  1 <= k <= 128.  With ``segments`` (a ``LinkSegments``; include/hgin.h A19) a
+    query's candidates are only the destinations of its source's own graph; a source whose graph has no destination
+    gets a fully padded row.  No gradient."""
     what = "link_topk"
     for name, z in (("z_src", z_src), ("z_dst", z_dst)):
         if z.dtype != torch.float32:
@@ -506,6 +695,8 @@ def link_topk(z_src: Tensor, z_dst: Tensor, src: Tensor, k: int, known: Tensor =
         raise RuntimeError(f"{what}: embedding widths differ")
     if src.dtype != torch.long or src.dim() != 1:
         raise ValueError(f"{what}: src must be an int64 [Q] tensor, got {src.dtype} {tuple(src.shape)}")
+    if segments is not None:
+        _check_segments(what, segments, z_src.size(0), z_dst.size(0))
     ops.require_device(z_src, z_dst, src, known, what=what)
     Q, k = int(src.numel()), int(k)
     n_src, n_dst, F = int(z_src.size(0)), int(z_dst.size(0)), int(z_src.size(1))
@@ -527,6 +718,13 @@ def link_topk(z_src: Tensor, z_dst: Tensor, src: Tensor, k: int, known: Tensor =
     _lib.check(_lib.lib().hgin_link_topk_workspace_size(Q, n_dst, F, k, ctypes.byref(nbytes)),
                "hgin_link_topk_workspace_size")
     ws = ops._workspace(nbytes.value, dev)
+    if segments is not None:
+        ops.require_device(segments.src_seg, what=what)
+        _lib.call("hgin_link_topk_seg_f32", ops._p(src), Q, n_src, n_dst, ops._p(z_src), z_src.stride(0), ops._p(z_dst),
+                  z_dst.stride(0), F, ops._p(rowptr), ops._p(col), k, ops._p(idx), ops._p(score), ops._p(ws),
+                  nbytes.value, ops._p(segments.src_seg), ops._p(segments.dst_ptr), segments.n_graphs,
+                  ops._stream(idx))
+        return idx, score
     _lib.call("hgin_link_topk_f32", ops._p(src), Q, n_src, n_dst, ops._p(z_src), z_src.stride(0), ops._p(z_dst),
               z_dst.stride(0), F, ops._p(rowptr), ops._p(col), k, ops._p(idx), ops._p(score), ops._p(ws),
               nbytes.value, ops._stream(idx))
@@ -540,8 +738,22 @@ def hard_negatives(z_src: Tensor, z_dst: Tensor, pos: Tensor, m: int, known: Ten
     (score descending, index ascending): ``link_topk`` on the unique sources of ``pos``, gathered back per positive.
     A source with fewer than m such destinations leaves padded slots; slot (e, j) is then filled with the uniform
     draw ``sample_negative_dst(E * m, n_dst, seed, offset)[e * m + j]``, which is not filtered and may be a known
-    edge.  1 <= m <= 128.  No gradient."""
-    what = "hard_negatives"
+    edge.  1 <= m <= 128.  No gradient.  ``hard_negatives_seg`` is the graph-local form."""
+    return _hard_negatives("hard_negatives", z_src, z_dst, pos, m, known, seed, offset, None)
+
+
+def hard_negatives_seg(z_src: Tensor, z_dst: Tensor, pos: Tensor, m: int, segments: LinkSegments, known: Tensor = None,
+                       seed: int = 0, offset: int = 0) -> Tensor:
+    """``hard_negatives`` inside each positive's own graph (``segments``: a ``LinkSegments``; include/hgin.h A19): the
+    mining goes through the segmented ``link_topk`` and the padded slots take the segmented draws of the same stream
+    (counter offset + e * m + j), so every entry lies in its positive's graph.  A function of its own, and not a
+    ``segments=`` on ``hard_negatives``, whose parameter list is a fixed part of the public surface."""
+    if not isinstance(segments, LinkSegments):
+        raise TypeError(f"hard_negatives_seg: segments must be a LinkSegments, got {type(segments).__name__}")
+    return _hard_negatives("hard_negatives_seg", z_src, z_dst, pos, m, known, seed, offset, segments)
+
+
+def _hard_negatives(what, z_src, z_dst, pos, m, known, seed, offset, segments):
     m = int(m)
     if not 1 <= m <= TOPK_MAX:
         raise ValueError(f"{what}: need 1 <= m <= {TOPK_MAX}, got m = {m}")
@@ -549,11 +761,18 @@ def hard_negatives(z_src: Tensor, z_dst: Tensor, pos: Tensor, m: int, known: Ten
     E, n_dst = int(pos.size(1)), int(z_dst.size(0))
     if E < 1 or E * m >= 2**31:
         raise ValueError(f"{what}: need E >= 1 and E * m < 2^31 (E = {E}, m = {m})")
+    if segments is not None:
+        _check_segments(what, segments, z_src.size(0), n_dst, pos)
     ops.require_device(z_src, z_dst, pos, known, what=what)
     src, inverse = torch.unique(pos[0], return_inverse=True)
-    idx, _ = link_topk(z_src, z_dst, src, m, pos if known is None else known)
-    mined = idx[inverse]
-    fill = sample_negative_dst(E * m, n_dst, seed, offset, mined.device).view(E, m)
+    if segments is not None:
+        idx, _ = link_topk(z_src, z_dst, src, m, pos if known is None else known, segments=segments)
+        mined = idx[inverse]
+        fill = _sample_seg(pos[0], m, seed, offset, segments).view(E, m)
+    else:
+        idx, _ = link_topk(z_src, z_dst, src, m, pos if known is None else known)
+        mined = idx[inverse]
+        fill = sample_negative_dst(E * m, n_dst, seed, offset, mined.device).view(E, m)
     out = torch.where(mined < 0, fill, mined).contiguous()
     _mark_checked(out, n_dst)   # in range by construction: no range-check sync when the set is used
     return out
@@ -567,10 +786,15 @@ class LinkPredictor:
 
     ``hard`` = m > 0 adds m mined negatives per positive (``hard_negatives``, filtered by the relation's edges) to
     the k uniform ones, and k may then be 0.  The set is kept as ``self.neg_dst``; ``loss`` re-mines it from the
-    step's own embeddings every ``mine_every`` steps (0: only ``mine`` changes it once it exists)."""
+    step's own embeddings every ``mine_every`` steps (0: only ``mine`` changes it once it exists).
+
+    ``graph_local`` = True is for a collated batch of independent graphs (``hgin.data.collate``, ``component_graph``):
+    ``LinkSegments.of(graph, relation)`` is built once per graph object and passed to ``loss``, ``mine``, ``metrics``,
+    ``full_metrics`` and ``predict``, so negatives, candidates and proposals stay inside each positive's / source's own
+    graph (include/hgin.h A19).  The default treats the destinations as one pool, as before."""
 
     def __init__(self, model, relation, k: int, seed: int, objective: str = "bce", temperature: float = 1.0,
-                 alpha: float = 1.0, hard: int = 0, mine_every: int = 1):
+                 alpha: float = 1.0, hard: int = 0, mine_every: int = 1, graph_local: bool = False):
         if not hasattr(model, "encode"):
             raise TypeError("LinkPredictor: the model has no encode(x_dict, edge_index_dict)")
         _objective("LinkPredictor", objective, temperature, alpha)
@@ -586,6 +810,16 @@ class LinkPredictor:
         self.hard, self.mine_every = hard, mine_every
         self.neg_dst = None       # the mined set, int32 [E, hard], of the positives self._mined_for
         self._mined_for = None
+        self.graph_local = bool(graph_local)
+        self._segments = None     # (graph, its LinkSegments) of the last graph seen with graph_local
+
+    def _seg_kw(self, graph) -> dict:
+        """{} by default (every call below is then exactly the unsegmented one), {"segments": ...} with graph_local."""
+        if not self.graph_local:
+            return {}
+        if self._segments is None or self._segments[0] is not graph:
+            self._segments = (graph, LinkSegments.of(graph, self.relation))
+        return {"segments": self._segments[1]}
 
     def _pos(self, graph, pos):
         return graph.edge_index[self.relation] if pos is None else pos
@@ -594,8 +828,12 @@ class LinkPredictor:
         """Padded slots are filled from the stream of seed + 1, apart from the uniform negatives' (seed)."""
         if known is None:
             known = graph.edge_index[self.relation]
-        self.neg_dst = hard_negatives(z[self.relation[0]].detach(), z[self.relation[2]].detach(), pos, self.hard,
-                                      known, self.seed + 1, offset)
+        zs, zd = z[self.relation[0]].detach(), z[self.relation[2]].detach()
+        if self.graph_local:
+            self.neg_dst = hard_negatives_seg(zs, zd, pos, self.hard, self._seg_kw(graph)["segments"], known,
+                                              self.seed + 1, offset)
+        else:
+            self.neg_dst = hard_negatives(zs, zd, pos, self.hard, known, self.seed + 1, offset)
         self._mined_for = pos
         return self.neg_dst
 
@@ -609,12 +847,13 @@ class LinkPredictor:
         offset = int(step) * int(pos.size(1)) * self.k
         if self.hard == 0:
             return sampled_link_loss(z[self.relation[0]], z[self.relation[2]], pos, self.k, self.seed, offset,
-                                     self.objective, self.temperature, self.alpha)
+                                     self.objective, self.temperature, self.alpha, **self._seg_kw(graph))
         if self.neg_dst is None or self._mined_for is not pos or \
                 (self.mine_every > 0 and int(step) % self.mine_every == 0):
             self._mine(z, graph, pos, None, int(step) * int(pos.size(1)) * self.hard)
         return sampled_link_loss(z[self.relation[0]], z[self.relation[2]], pos, self.k, self.seed, offset,
-                                 self.objective, self.temperature, self.alpha, neg_dst=self.neg_dst)
+                                 self.objective, self.temperature, self.alpha, neg_dst=self.neg_dst,
+                                 **self._seg_kw(graph))
 
     def mine(self, graph, pos: Tensor = None, known: Tensor = None) -> Tensor:
         """Mine ``self.neg_dst`` now, from an eval-mode encode without gradients (the mode is restored), as
@@ -643,8 +882,9 @@ class LinkPredictor:
                 z = self.model.encode(graph.x_dict(), graph.edge_index_dict())
                 if neg_dst is not None:
                     return link_metrics(z[self.relation[0]], z[self.relation[2]], pos, self.k, self.seed,
-                                        neg_dst=neg_dst)
-                return link_metrics(z[self.relation[0]], z[self.relation[2]], pos, self.k, self.seed)
+                                        neg_dst=neg_dst, **self._seg_kw(graph))
+                return link_metrics(z[self.relation[0]], z[self.relation[2]], pos, self.k, self.seed,
+                                    **self._seg_kw(graph))
         finally:
             self.model.train(was_training)
 
@@ -660,7 +900,7 @@ class LinkPredictor:
         try:
             with torch.no_grad():
                 z = self.model.encode(graph.x_dict(), graph.edge_index_dict())
-                return link_full_metrics(z[self.relation[0]], z[self.relation[2]], pos, known)
+                return link_full_metrics(z[self.relation[0]], z[self.relation[2]], pos, known, **self._seg_kw(graph))
         finally:
             self.model.train(was_training)
 
@@ -678,6 +918,6 @@ class LinkPredictor:
                 z_src, z_dst = z[self.relation[0]], z[self.relation[2]]
                 if src is None:
                     src = torch.arange(z_src.size(0), dtype=torch.long, device=z_src.device)
-                return link_topk(z_src, z_dst, src, k, known)
+                return link_topk(z_src, z_dst, src, k, known, **self._seg_kw(graph))
         finally:
             self.model.train(was_training)

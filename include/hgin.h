@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HGIN_ABI_VERSION 13
+#define HGIN_ABI_VERSION 14
 
 #define HGIN_OK 0
 #define HGIN_E_ARG (-1)        /* bad size / null pointer / unsupported combination */
@@ -598,6 +598,64 @@ int hgin_link_topk_f32(const int64_t* src, int64_t n_query, int64_t n_src, int64
                        int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F, const int32_t* known_rowptr,
                        const int32_t* known_col, int64_t k, int32_t* top_idx, float* top_score, void* ws,
                        size_t ws_bytes, void* stream);
+
+/* ---- A19: graph-local negatives and candidates (NOT IN REFERENCE; build-defined, ABI 14) --------------------------
+ * A collated batch of G graphs (hgin.data.collate) keeps each graph's rows of a node type in one contiguous block.
+ * The segmentation of a relation is src_seg int32 [n_src] (the graph of every source row, any order) and dst_ptr int32
+ * [G + 1] (dst_ptr[0] = 0, dst_ptr[G] = n_dst, non-decreasing: graph g owns the destinations dst_ptr[g] ..
+ * dst_ptr[g + 1] - 1; empty graphs are allowed).  For a source s: g = src_seg[s], lo = dst_ptr[g],
+ * n = dst_ptr[g + 1] - lo.  The *_seg entry points are their A10 / A13 / A14 / A15 / A16 / A17 / A18 counterparts
+ * under this rule; the unsegmented entry points, their launches and their bits are unchanged.
+ *   Draw.  The negative with Philox counter c is lo + hi32(word(c) * n), word(c) = the word A10 uses at the same
+ *     counter (block c >> 2, word c & 3, key = seed), c = offset + e k + t - 1 as in A13.  With G = 1 (lo = 0,
+ *     n = n_dst) every draw is bit for bit A10's.
+ *   Candidates of a query (s, d): the destinations c in [lo, lo + n) with c != d and (s, c) not a known edge.  Known
+ *     edges that leave the graph are never candidates and are not subtracted:
+ *     n_cand = n - 1 - |distinct known neighbours of s inside [lo, lo + n) other than d|.
+ *   Top-K candidates of a query s: the destinations in [lo, lo + n) that are not known neighbours of s; a query whose
+ *     graph has no destination (n = 0) returns a fully padded row (idx -1, score -inf).
+ * The caller guarantees 0 <= src_seg < G, a valid dst_ptr and, where there are positives, that every positive's
+ * destination lies in its source's graph (so n >= 1 there); device data is not checked.  Nothing is read out of range
+ * even so: g is clamped into [0, G), dst_ptr values into [0, n_dst], a drawn id into [0, n_dst) as A15's clamp_id does.
+ *   hgin_neg_sample_seg: out int32 [E k], draw i belongs to positive i / k (src = its source ids, int64 [E]) and has
+ *     counter offset + i.
+ *   hgin_link_loss_fwd_seg_f32: A18's argument list plus the segmentation; neg_dst = NULL with m = 0 is allowed (then
+ *     k >= 1), and every objective is served.  One src_seg load and two dst_ptr loads per positive; pair batching,
+ *     Philox window, scores, loss terms, summation order and the coef / neg layout are A13 / A17 / A18's, so both
+ *     backward entry points serve it unchanged and a segmented draw carries the bits the same destination carries as
+ *     a given negative.
+ *   hgin_link_rank_seg_f32: A14 / A18's ranks over the segmented draws (neg_dst = NULL with m = 0 allowed).
+ *   hgin_link_full_rank_seg_f32: A15 over the candidates above.  Threshold pre-pass as A15; in the sweep a lane
+ *     compares a destination only inside its query column's segment, and a workgroup visits only the tiles
+ *     min lo / 128 .. ceil(max hi / 128) of its 128 queries (block-wide min / max; each split takes a slice of that
+ *     range, an empty slice returns at once), so queries sorted by graph cost E n_dst / G instead of E n_dst; the
+ *     filter subtracts a known neighbour only inside the segment.  Scores keep A15's K order: a (query row,
+ *     destination row) pair carries the bits it carries unsegmented, wherever its tile lies.
+ *   hgin_link_topk_seg_f32: A16 with the same tile range; the in-segment test sits in the insertion path.  Workspace
+ *     as hgin_link_topk_workspace_size (the per-list counts are zeroed first: a workgroup with an empty slice writes
+ *     none).
+ * Additional status: HGIN_E_ARG for src_seg / dst_ptr = NULL or n_graphs outside [1, 2^31). */
+int hgin_neg_sample_seg(uint64_t seed, uint64_t offset, const int64_t* src, int64_t n_pos, int64_t k,
+                        const int32_t* src_seg, const int32_t* dst_ptr, int64_t n_graphs, int32_t* out, void* stream);
+int hgin_link_loss_fwd_seg_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64_t seed, uint64_t offset,
+                               int64_t n_dst, const int32_t* neg_dst, int64_t m, const float* z_src, int64_t ld_src,
+                               const float* z_dst, int64_t ld_dst, int64_t F, float* coef, int64_t* neg, float* loss,
+                               void* workspace, size_t workspace_bytes, int32_t objective, float param,
+                               const int32_t* src_seg, const int32_t* dst_ptr, int64_t n_graphs, void* stream);
+int hgin_link_rank_seg_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64_t seed, uint64_t offset,
+                           int64_t n_dst, const int32_t* neg_dst, int64_t m, const float* z_src, int64_t ld_src,
+                           const float* z_dst, int64_t ld_dst, int64_t F, int32_t* n_greater, int32_t* n_equal,
+                           const int32_t* src_seg, const int32_t* dst_ptr, int64_t n_graphs, void* stream);
+int hgin_link_full_rank_seg_f32(const int64_t* pos, int64_t n_pos, int64_t n_src, int64_t n_dst, const float* z_src,
+                                int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F,
+                                const int32_t* known_rowptr, const int32_t* known_col, int32_t* n_greater,
+                                int32_t* n_equal, int32_t* n_cand, void* ws, size_t ws_bytes, const int32_t* src_seg,
+                                const int32_t* dst_ptr, int64_t n_graphs, void* stream);
+int hgin_link_topk_seg_f32(const int64_t* src, int64_t n_query, int64_t n_src, int64_t n_dst, const float* z_src,
+                           int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F, const int32_t* known_rowptr,
+                           const int32_t* known_col, int64_t k, int32_t* top_idx, float* top_score, void* ws,
+                           size_t ws_bytes, const int32_t* src_seg, const int32_t* dst_ptr, int64_t n_graphs,
+                           void* stream);
 
 /* ---- F4 widening: HetroGAT's graph attention (models.py:380-506, PyG 2.0.2 GATConv) ---------------------------
  * x_s / x_d: projected source / destination features [N, H * C] (row stride ld*), edges = the relation after

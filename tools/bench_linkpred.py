@@ -24,9 +24,14 @@ with the M negatives mined by ``hard_negatives`` from the (random) embeddings; e
 alone.  Mining sweeps every destination for every distinct source, so the mined pair uses positives whose sources come
 from the first ``--mine-sources`` source rows (the random-given pair keeps the shape's own positives).
 
+``--graphs G`` (include/hgin.h A19; default 1: everything above, unchanged) cuts every shape into G equal graphs with
+the positives sorted by graph and times the fused step with ``segments=`` against the same step without it, on the
+same tensors, alternating in one run.
+
     python tools/bench_linkpred.py --out profiles/linkpred/linkpred_bench.json
     python tools/bench_linkpred.py --k 1 --hard 4 --out profiles/linkpred/linkhard_bench.json
     python tools/bench_linkpred.py --objective all --out profiles/linkpred/linkobj_bench.json
+    python tools/bench_linkpred.py --graphs 8      # profiles/linkseg/linkrank_seg_bench.json, "loss_step"
     python tools/bench_linkpred.py --configs cfg1 --scale 0.1 --k 1      # a tiny run
 """
 import argparse
@@ -257,9 +262,78 @@ def run_hard(torch, shape, M, repeats, warmup, target_ms, mine_sources, seed=123
     return out
 
 
+def split_graphs(n_src: int, n_dst: int, E: int, graphs: int, seed: int, device="cpu"):
+    """A shape cut into ``graphs`` equal graphs (the first n % graphs blocks one row longer), as a collated batch
+    lays them out: (pos int64 [2, E], batch_src int64 [n_src], batch_dst int64 [n_dst]).  Graph e * graphs // E owns
+    positive e, so the positives come sorted by graph; source and destination are uniform inside the graph's blocks."""
+    import torch
+    if not 1 <= graphs <= min(n_src, n_dst):
+        raise SystemExit(f"--graphs must be in [1, min(n_src, n_dst)] = [1, {min(n_src, n_dst)}], got {graphs}")
+    g = torch.Generator(device=device).manual_seed(seed)
+
+    def blocks(n):
+        sizes = torch.tensor([n // graphs + (i < n % graphs) for i in range(graphs)], dtype=torch.long, device=device)
+        ptr = torch.zeros(graphs + 1, dtype=torch.long, device=device)
+        ptr[1:] = torch.cumsum(sizes, 0)
+        return sizes, ptr
+
+    (ss, sp), (ds, dp) = blocks(n_src), blocks(n_dst)
+    ge = (torch.arange(E, dtype=torch.long, device=device) * graphs) // max(E, 1)
+    u = torch.rand(2, E, generator=g, device=device, dtype=torch.float64)
+    src = sp[ge] + torch.minimum((u[0] * ss[ge]).long(), ss[ge] - 1)
+    dst = dp[ge] + torch.minimum((u[1] * ds[ge]).long(), ds[ge] - 1)
+    ids = torch.arange(graphs, dtype=torch.long, device=device)
+    return torch.stack([src, dst]), torch.repeat_interleave(ids, ss), torch.repeat_interleave(ids, ds)
+
+
+def run_graphs(torch, shape, graphs, repeats, warmup, target_ms, seed=1234):
+    """The ``--graphs G`` measurements of one shape: the shape cut into G equal graphs, positives sorted by graph, the
+    fused forward + backward step with ``segments=`` against the same step without it on the same tensors, the paths
+    alternating in one run."""
+    from hgin.linkpred import LinkSegments, sampled_link_loss
+    dev = "cuda"
+    n_src, n_dst, E, F, k = (shape[x] for x in ("n_src", "n_dst", "E", "F", "k"))
+    pos, batch_src, batch_dst = split_graphs(n_src, n_dst, E, graphs, seed, dev)
+    seg = LinkSegments(batch_src, batch_dst, graphs)
+    g = torch.Generator(device=dev).manual_seed(seed)
+    z_src = (torch.randn(n_src, F, generator=g, device=dev) * 0.1).requires_grad_(True)
+    z_dst = (torch.randn(n_dst, F, generator=g, device=dev) * 0.1).requires_grad_(True)
+
+    def step_of(kw):
+        def fn(step):
+            z_src.grad = z_dst.grad = None
+            sampled_link_loss(z_src, z_dst, pos, k, seed, step * E * k, **kw).backward()
+        return fn
+
+    paths = {"unsegmented": step_of({}), "segmented": step_of({"segments": seg})}
+    for s in range(warmup):
+        for fn in paths.values():
+            fn(s)
+    torch.cuda.synchronize()
+    inner = {name: _inner_for(torch, fn, target_ms) for name, fn in paths.items()}
+    times, step = {name: [] for name in paths}, warmup
+    for _ in range(repeats):      # the paths alternate
+        for name, fn in paths.items():
+            times[name].append(_timed(torch, fn, inner[name], step))
+        step += max(inner.values())
+    out = dict(shape, graphs=graphs, positives="sorted by graph")
+    for name in paths:
+        out[name] = dict(_stats(times[name]), inner=inner[name])
+    a, b = out["segmented"], out["unsegmented"]
+    out["segmented_over_unsegmented"] = a["median_ms"] / b["median_ms"]
+    out["segmented_within_spread_of_unsegmented"] = a["min_ms"] <= b["max_ms"] and b["min_ms"] <= a["max_ms"]
+    z_src.grad = z_dst.grad = None
+    del z_src, z_dst, pos
+    torch.cuda.empty_cache()
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--configs", default="cfg2,cfg3")
+    ap.add_argument("--graphs", type=int, default=1,
+                    help="cut every shape into G equal graphs, positives sorted by graph, and time the fused step with "
+                         "segments= against the same step without (include/hgin.h A19); 1: today's measurements")
     ap.add_argument("--k", default="1,4")
     ap.add_argument("--scale", type=float, default=1.0, help="multiply every node / edge count (tiny runs)")
     ap.add_argument("--repeats", type=int, default=7)
@@ -275,6 +349,8 @@ def main(argv=None) -> int:
         ap.error("--repeats must be at least 5")
     if args.hard is not None and not 1 <= args.hard <= 128:
         ap.error("--hard must be in [1, 128]")
+    if args.graphs < 1:
+        ap.error("--graphs must be at least 1")
     objectives = objectives_of(args.objective)
     shapes = plan(args.configs.split(","), [int(v) for v in args.k.split(",")], args.scale)
     for s in shapes:
@@ -286,6 +362,16 @@ def main(argv=None) -> int:
         return 2
     from hgin import _lib
     _lib.lib()
+    if args.graphs > 1:
+        results = [run_graphs(torch, s, args.graphs, args.repeats, args.warmup, args.target_ms) for s in shapes]
+        doc = {"tool": "tools/bench_linkpred.py", "device": torch.cuda.get_device_name(0), "repeats": args.repeats,
+               "warmup": args.warmup, "graphs": args.graphs, "shapes": results}
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(json.dumps(doc, indent=1) + "\n")
+        print(json.dumps(doc))
+        return 0
     if args.hard is not None:
         results = [run_hard(torch, s, args.hard, args.repeats, args.warmup, args.target_ms, args.mine_sources)
                    for s in shapes]

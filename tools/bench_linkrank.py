@@ -15,7 +15,11 @@ it uses, and how many queries the two paths count differently (torch's GEMM roun
 There is no CPU fallback: without a HIP device the tool prints the plan and fails.
 
     python tools/bench_linkrank.py --out profiles/linkrank/linkrank_bench.json
+    python tools/bench_linkrank.py --graphs 8      # profiles/linkseg/linkrank_seg_bench.json, "full_rank_sweep"
     python tools/bench_linkrank.py --configs cfg1 --scale 0.1 --queries 64      # a tiny run
+
+``--graphs G`` (include/hgin.h A19; default 1: everything above, unchanged) cuts the relation into G equal graphs with
+the queries sorted by graph and times ``link_full_ranks`` with ``segments=`` against the same call without it.
 """
 import argparse
 import importlib.util
@@ -84,6 +88,52 @@ def _known_pairs(torch, pos_q, rowptr, col, chunk_rows):
     return qi, c, torch.searchsorted(qi, bounds).tolist()
 
 
+def split_graphs(n_src, n_dst, E, graphs, seed, device="cpu"):
+    """tools/bench_linkpred.py's cut of a shape into ``graphs`` equal graphs, positives sorted by graph."""
+    return _linkpred_tool().split_graphs(n_src, n_dst, E, graphs, seed, device)
+
+
+def run_graphs(torch, shape, graphs, repeats, warmup, target_ms, seed=1234):
+    """The ``--graphs G`` measurements of one shape: the relation cut into G equal graphs, the queries Q positives
+    sorted by graph (every 128-query block then covers about n_dst / G destinations), the known edges the whole
+    relation; ``link_full_ranks`` with ``segments=`` against the same call without it on the same tensors, unfiltered
+    and filtered, alternating in one run."""
+    lp = _linkpred_tool()
+    from hgin.linkpred import LinkSegments, link_full_ranks
+    dev = "cuda"
+    n_src, n_dst, E, F, Q = (shape[x] for x in ("n_src", "n_dst", "E", "F", "Q"))
+    known, batch_src, batch_dst = split_graphs(n_src, n_dst, E, graphs, seed, dev)
+    seg = LinkSegments(batch_src, batch_dst, graphs)
+    pick = (torch.arange(Q, dtype=torch.long, device=dev) * E) // Q   # Q positives spread over every graph, in order
+    pos = known[:, pick].contiguous()
+    g = torch.Generator(device=dev).manual_seed(seed)
+    z_src = torch.randn(n_src, F, generator=g, device=dev) * 0.1
+    z_dst = torch.randn(n_dst, F, generator=g, device=dev) * 0.1
+    paths = {"unsegmented_unfiltered": lambda _: link_full_ranks(z_src, z_dst, pos),
+             "segmented_unfiltered": lambda _: link_full_ranks(z_src, z_dst, pos, segments=seg),
+             "unsegmented_filtered": lambda _: link_full_ranks(z_src, z_dst, pos, known),
+             "segmented_filtered": lambda _: link_full_ranks(z_src, z_dst, pos, known, segments=seg)}
+    for _ in range(warmup):
+        for fn in paths.values():
+            fn(0)
+    torch.cuda.synchronize()
+    inner = {name: lp._inner_for(torch, fn, target_ms) for name, fn in paths.items()}
+    times = {name: [] for name in paths}
+    for _ in range(repeats):      # the paths alternate
+        for name, fn in paths.items():
+            times[name].append(lp._timed(torch, fn, inner[name], 0))
+    out = dict(shape, graphs=graphs, queries="sorted by graph")
+    for name in paths:
+        out[name] = dict(lp._stats(times[name]), inner=inner[name])
+    for kind in ("unfiltered", "filtered"):
+        a, b = out["segmented_" + kind], out["unsegmented_" + kind]
+        out[f"segmented_over_unsegmented_{kind}"] = a["median_ms"] / b["median_ms"]
+        out[f"segmented_faster_beyond_spread_{kind}"] = a["max_ms"] < b["min_ms"]
+    del z_src, z_dst, pos, known
+    torch.cuda.empty_cache()
+    return out
+
+
 def run_shape(torch, shape, repeats, warmup, target_ms, seed=1234):
     lp = _linkpred_tool()
     from hgin.linkpred import _known_csr, link_full_ranks
@@ -138,12 +188,17 @@ def main(argv=None) -> int:
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--target-ms", type=float, default=30.0, help="device time of one timed repeat, at least")
+    ap.add_argument("--graphs", type=int, default=1,
+                    help="cut every shape into G equal graphs, queries sorted by graph, and time link_full_ranks with "
+                         "segments= against the same call without (include/hgin.h A19); 1: today's measurements")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     if args.repeats < 5:
         ap.error("--repeats must be at least 5")
     if args.queries < 1 or args.warmup < 1:
         ap.error("--queries and --warmup must be at least 1")
+    if args.graphs < 1:
+        ap.error("--graphs must be at least 1")
     shapes = plan(args.configs.split(","), args.queries, args.scale)
     for s in shapes:
         print("plan:", json.dumps(s), file=sys.stderr)
@@ -154,6 +209,16 @@ def main(argv=None) -> int:
         return 2
     from hgin import _lib
     _lib.lib()
+    if args.graphs > 1:
+        results = [run_graphs(torch, s, args.graphs, args.repeats, args.warmup, args.target_ms) for s in shapes]
+        doc = {"tool": "tools/bench_linkrank.py", "device": torch.cuda.get_device_name(0), "repeats": args.repeats,
+               "warmup": args.warmup, "graphs": args.graphs, "shapes": results}
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(json.dumps(doc, indent=1) + "\n")
+        print(json.dumps(doc))
+        return 0
     results = [run_shape(torch, s, args.repeats, args.warmup, args.target_ms) for s in shapes]
     flags = [r[f"fused_faster_beyond_spread_{k}"] for r in results for k in ("unfiltered", "filtered")]
     doc = {"tool": "tools/bench_linkrank.py", "device": torch.cuda.get_device_name(0),
