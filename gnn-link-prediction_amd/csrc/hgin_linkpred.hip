@@ -100,6 +100,113 @@ __global__ __launch_bounds__(256) void k_neg_sample_seg(uint64_t seed, uint64_t 
   }
 }
 
+// ---- A20: draws from a source's non-neighbours ---------------------------------------------------------------------
+// first index in [b, e) whose column is >= v (e if none); reads col[b .. e) only and ends whatever the columns hold
+__device__ __forceinline__ int32_t col_lower_bound(const int32_t* __restrict__ col, int32_t b, int32_t e, int64_t v) {
+  while (b < e) {
+    const int32_t mid = b + ((e - b) >> 1);
+    if ((int64_t)col[mid] < v) b = mid + 1;
+    else e = mid;
+  }
+  return b;
+}
+
+// The known row of source s clipped to its draw window [lo, lo + n): col[cb .. cb + d) are the row's columns inside the
+// window, f = n - d the free destinations (0 when the row covers the window, or claims more than it holds).  s is
+// clamped into [0, n_src) as seg_of clamps g; clip = false (one pool: the window is every destination) takes the row
+// whole.  rowptr == NULL: no known edges.
+__device__ __forceinline__ void filt_row(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                         int64_t n_src, int64_t s, bool clip, uint32_t lo, uint32_t n, int32_t& cb,
+                                         int32_t& d, uint32_t& f) {
+  cb = 0;
+  d = 0;
+  if (rowptr != nullptr) {
+    s = s < 0 ? 0 : (s >= n_src ? n_src - 1 : s);
+    const int32_t rb = rowptr[s];
+    int32_t re = rowptr[s + 1];
+    re = re < rb ? rb : re;
+    cb = rb;
+    int32_t ce = re;
+    if (clip) {
+      cb = col_lower_bound(col, rb, re, (int64_t)lo);
+      ce = col_lower_bound(col, cb, re, (int64_t)lo + (int64_t)n);
+    }
+    d = ce - cb;
+  }
+  f = (uint32_t)d < n ? n - (uint32_t)d : 0u;
+}
+
+// N draws of one positive from Philox words w (slots with on[u] false are skipped and return 0).  f == 0: the
+// unfiltered draw lo + hi32(w n).  Otherwise r = hi32(w f) and j = how many of the window's columns c_i have
+// (c_i - lo) - i <= r (that sequence is non-decreasing, so a binary search over crow[0 .. d) finds it); the draw is
+// lo + r + j, the r-th free destination.  The search's interval lengths do not depend on the data, so the N searches
+// advance together and each step is one batch of independent loads; every index stays inside [0, d), and r + j < n
+// whatever the columns hold.  The result is kept below n_dst as reduce_seg keeps it.
+template <int N>
+__device__ __forceinline__ void filt_draws(const uint32_t (&w)[N], const bool (&on)[N],
+                                           const int32_t* __restrict__ crow, int32_t d, uint32_t f, uint32_t lo,
+                                           uint32_t n, uint32_t n_dst, int32_t (&out)[N]) {
+  if (f == 0u) {
+#pragma unroll
+    for (int u = 0; u < N; ++u) out[u] = on[u] ? reduce_seg(w[u], lo, n, n_dst) : 0;
+    return;
+  }
+  uint32_t r[N];
+  int32_t j[N];
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+    r[u] = (uint32_t)reduce_range(w[u], f);
+    j[u] = 0;
+  }
+  int32_t len = d;
+  while (len > 0) {
+    const int32_t half = len > 1 ? len >> 1 : 1;   // probe j + half - 1; the last step (len == 1) probes j itself
+    int32_t c[N];
+#pragma unroll
+    for (int u = 0; u < N; ++u) c[u] = on[u] ? crow[j[u] + half - 1] : 0;
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+      const int64_t v = (int64_t)c[u] - (int64_t)lo - (int64_t)(j[u] + half - 1);
+      if (on[u] && v <= (int64_t)r[u]) j[u] += half;
+    }
+    len -= half;
+  }
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+    const uint32_t v = lo + r[u] + (uint32_t)j[u];
+    out[u] = on[u] ? (int32_t)(v < n_dst ? v : n_dst - 1) : 0;
+  }
+}
+
+// A20 sampler: k_neg_sample_seg's thread-per-draw form; n_graphs == 0: one pool of n_dst destinations.
+__global__ __launch_bounds__(256) void k_neg_sample_filt(uint64_t seed, uint64_t offset,
+                                                         const int64_t* __restrict__ src, int64_t n, int k,
+                                                         uint32_t n_dst, const int32_t* __restrict__ src_seg,
+                                                         const int32_t* __restrict__ dst_ptr, int n_graphs,
+                                                         int64_t n_src, const int32_t* __restrict__ known_rowptr,
+                                                         const int32_t* __restrict__ known_col,
+                                                         int32_t* __restrict__ out) {
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const uint64_t c = offset + (uint64_t)i;
+    const uint64_t b = c >> 2;
+    const U4 x = philox4x32_10(U4{(uint32_t)b, (uint32_t)(b >> 32), 0u, 0u}, k0, k1);
+    const int64_t s = src[i / k];
+    uint32_t lo = 0u, cnt = n_dst;
+    if (n_graphs > 0) seg_of(src_seg, dst_ptr, n_graphs, s, lo, cnt);
+    int32_t cb, d;
+    uint32_t f;
+    filt_row(known_rowptr, known_col, n_src, s, n_graphs > 0, lo, cnt, cb, d, f);
+    const uint32_t wsel = (uint32_t)c & 3u;
+    const uint32_t w[1] = {wsel == 0 ? x.x : (wsel == 1 ? x.y : (wsel == 2 ? x.z : x.w))};
+    const bool on[1] = {true};
+    int32_t v[1];
+    filt_draws<1>(w, on, known_col + cb, d, f, lo, cnt, n_dst, v);
+    out[i] = v[0];
+  }
+}
+
 template <int VEC, int G>
 __global__ __launch_bounds__(256) void k_dot_fwd(const int32_t* __restrict__ src, const int32_t* __restrict__ dst,
                                                  int64_t n_pairs, const float* __restrict__ zs, int64_t lds,
@@ -242,7 +349,12 @@ __device__ __forceinline__ float soft_arg(float s, float scale) {
 // A19 (SEG): a draw of positive e lands in the destinations of its source's graph, lo + hi32(word * n) in place of
 // hi32(word * n_dst): one src_seg load and two dst_ptr loads per positive, nothing else differs.  Without SEG
 // src_seg / dst_ptr / n_graphs are not read.
-template <int VEC, int G, bool ONE, bool RANK, int OBJ, bool GIVEN, bool SEG>
+//
+// A20 (FILT): a draw of positive e is the r-th destination of its window that is not a known neighbour of its source
+// (filt_row once per positive, filt_draws per batch of drawn pairs; given pairs are not searched).  Instantiated in
+// its GIVEN and SEG form only: m == 0 (no given pair) and n_graphs == 0 (one pool, src_seg / dst_ptr not read) are
+// run-time cases.  Without FILT n_src / known_rowptr / known_col are not read.
+template <int VEC, int G, bool ONE, bool RANK, int OBJ, bool GIVEN, bool SEG, bool FILT = false>
 __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ pos, int64_t E, int k, uint64_t seed,
                                                   uint64_t offset, uint32_t n_dst, const float* __restrict__ zs,
                                                   int64_t lds, const float* __restrict__ zd, int64_t ldd, int F,
@@ -251,7 +363,10 @@ __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ po
                                                   int32_t* __restrict__ n_gt, int32_t* __restrict__ n_eq,
                                                   const int32_t* __restrict__ given, int m,
                                                   const int32_t* __restrict__ src_seg,
-                                                  const int32_t* __restrict__ dst_ptr, int n_graphs) {
+                                                  const int32_t* __restrict__ dst_ptr, int n_graphs,
+                                                  int64_t n_src, const int32_t* __restrict__ known_rowptr,
+                                                  const int32_t* __restrict__ known_col) {
+  static_assert(!FILT || (GIVEN && SEG), "the filtered kernel exists in its GIVEN and SEG form only");
   constexpr bool TWO_PHASE = !RANK && (OBJ == kObjSoftmax || OBJ == kObjSelfAdv);
   constexpr bool POS_IS_SUM = !RANK && (OBJ == kObjSoftmax || OBJ == kObjBpr);
   constexpr int EPW = 64 / G;   // edges per wave
@@ -272,7 +387,13 @@ __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ po
     const int64_t s0 = pos[e];
     const float* a = zs + s0 * lds;
     uint32_t seg_lo = 0u, seg_n = n_dst;
-    if constexpr (SEG) seg_of(src_seg, dst_ptr, n_graphs, s0, seg_lo, seg_n);
+    if constexpr (SEG) {
+      if (!FILT || n_graphs > 0) seg_of(src_seg, dst_ptr, n_graphs, s0, seg_lo, seg_n);
+    }
+    // A20 state of this positive: its known row inside the window and the count of free destinations
+    int32_t f_cb = 0, f_d = 0;
+    uint32_t f_free = seg_n;
+    if constexpr (FILT) filt_row(known_rowptr, known_col, n_src, s0, n_graphs > 0, seg_lo, seg_n, f_cb, f_d, f_free);
     // pair t's loss term, coefficient and (t >= 1) drawn pair; e = exp(-|s|) serves softplus and sigmoid alike
     auto finish_pair = [&](int t, float s, int64_t idm) {
       const float ex = expf(-fabsf(s));
@@ -384,18 +505,32 @@ __global__ __launch_bounds__(256) void k_link_fwd(const int64_t* __restrict__ po
         }
       }
       int64_t id[kInFlight];
+      uint32_t f_w[kInFlight];   // FILT: the words of the batch's drawn pairs
+      bool f_on[kInFlight];
 #pragma unroll
       for (int u = 0; u < kInFlight; ++u) {
         const int t = t0 + u;
         id[u] = d0;
+        f_w[u] = 0u;
+        f_on[u] = false;
         if (t >= 1 && t <= k) {
           const uint64_t c = base + (uint64_t)(t - 1);
           const uint32_t wx = word_of(X, (uint32_t)c & 3u), wy = word_of(Y, (uint32_t)c & 3u);
           const uint32_t r = (c >> 2) == b0 ? wx : wy;
-          if constexpr (SEG) id[u] = reduce_seg(r, seg_lo, seg_n, n_dst);
+          if constexpr (FILT) { f_w[u] = r; f_on[u] = true; }
+          else if constexpr (SEG) id[u] = reduce_seg(r, seg_lo, seg_n, n_dst);
           else id[u] = reduce_range(r, n_dst);
         } else if (GIVEN && t > k && t <= K) {
           id[u] = g_cur[u];
+        }
+      }
+      if constexpr (FILT) {
+        if (tf <= k) {   // uniform: a batch of given pairs only searches nothing
+          int32_t f_id[kInFlight];
+          filt_draws<kInFlight>(f_w, f_on, known_col + f_cb, f_d, f_free, seg_lo, seg_n, n_dst, f_id);
+#pragma unroll
+          for (int u = 0; u < kInFlight; ++u)
+            if (f_on[u]) id[u] = f_id[u];
         }
       }
       float sc[kInFlight];
@@ -782,12 +917,13 @@ int link_common_checks(const char* what, const int64_t* pos, int64_t E, int64_t 
 }
 
 // GIVEN (A18): k uniform draws + m given destinations per positive (given int32 [E, m]); otherwise m = 0.
-template <bool RANK, int OBJ = kObjBce, bool GIVEN = false, bool SEG = false>
+template <bool RANK, int OBJ = kObjBce, bool GIVEN = false, bool SEG = false, bool FILT = false>
 void launch_link_fwd(const LinkShape& sh, hipStream_t s, const int64_t* pos, int64_t E, int k, uint64_t seed,
                      uint64_t offset, uint32_t n_dst, const float* z_src, int64_t ld_src, const float* z_dst,
                      int64_t ld_dst, int F, float* coef, int64_t* neg, float* partial, int32_t* n_gt, int32_t* n_eq,
                      float param = 0.0f, const int32_t* given = nullptr, int m = 0, const int32_t* src_seg = nullptr,
-                     const int32_t* dst_ptr = nullptr, int n_graphs = 0) {
+                     const int32_t* dst_ptr = nullptr, int n_graphs = 0, int64_t n_src = 0,
+                     const int32_t* known_rowptr = nullptr, const int32_t* known_col = nullptr) {
   const int K = k + m;
   float w_pos = (float)(0.5 / (double)E), w_neg = (float)(0.5 / ((double)E * (double)K)), xscale = 0.0f;
   if (OBJ == kObjSoftmax) {
@@ -800,12 +936,14 @@ void launch_link_fwd(const LinkShape& sh, hipStream_t s, const int64_t* pos, int
     xscale = param;
   }
   constexpr const char* kEpilogue[] = {"LOSS", "SOFTMAX", "BPR", "SELFADV"};
-  HGIN_TRACE("k_link_fwd<%d,%d,%s,%s%s%s>", sh.vec ? 4 : 1, sh.g, sh.one ? "ONE" : "LOOP",
-             RANK ? "RANK" : kEpilogue[OBJ], GIVEN ? ",GIVEN" : "", SEG ? ",SEG" : "");
+  // FILT is one instantiation (GIVEN, SEG): its tag names what the call uses of it, then ,FILT
+  HGIN_TRACE("k_link_fwd<%d,%d,%s,%s%s%s%s>", sh.vec ? 4 : 1, sh.g, sh.one ? "ONE" : "LOOP",
+             RANK ? "RANK" : kEpilogue[OBJ], GIVEN && (!FILT || m > 0) ? ",GIVEN" : "",
+             SEG && (!FILT || n_graphs > 0) ? ",SEG" : "", FILT ? ",FILT" : "");
 #define HGIN_LINK_FWD(VEC_, G_, ONE_)                                                                               \
-  k_link_fwd<VEC_, G_, ONE_, RANK, OBJ, GIVEN, SEG><<<sh.grid, 256, 0, s>>>(                                         \
+  k_link_fwd<VEC_, G_, ONE_, RANK, OBJ, GIVEN, SEG, FILT><<<sh.grid, 256, 0, s>>>(                                   \
       pos, E, k, seed, offset, n_dst, z_src, ld_src, z_dst, ld_dst, F, w_pos, w_neg, xscale, coef, neg, partial, n_gt, \
-      n_eq, given, m, src_seg, dst_ptr, n_graphs)
+      n_eq, given, m, src_seg, dst_ptr, n_graphs, n_src, known_rowptr, known_col)
   if (sh.vec) {
     if (!sh.one) HGIN_LINK_FWD(4, 64, false);
     else HGIN_G_SWITCH(sh.g, HGIN_LINK_FWD(4, G, true))
@@ -1095,6 +1233,129 @@ extern "C" int hgin_link_rank_seg_f32(const int64_t* pos, int64_t n_pos, int64_t
                                                 (uint32_t)n_dst, z_src, ld_src, z_dst, ld_dst, (int)F, nullptr, nullptr,
                                                 nullptr, n_greater, n_equal, 0.0f, nullptr, 0, src_seg, dst_ptr,
                                                 (int)n_graphs);
+  return check_launch(what);
+}
+
+// ---- A20 entry points: draws from each source's non-neighbours ------------------------------------------------------
+namespace {
+
+// the window (n_graphs = 0 with src_seg = dst_ptr = NULL: one pool; otherwise A19's) and the known CSR
+int link_filt_window_checks(const char* what, const int32_t* src_seg, const int32_t* dst_ptr, int64_t n_graphs,
+                            int64_t n_src, const int32_t* known_rowptr, const int32_t* known_col) {
+  HGIN_ARG_CHECK(n_graphs >= 0 && n_graphs < (int64_t(1) << 31), "%s: n_graphs = %lld must be in [0, 2^31)", what,
+                 (long long)n_graphs);
+  if (n_graphs == 0) {
+    HGIN_ARG_CHECK(src_seg == nullptr && dst_ptr == nullptr, "%s: src_seg / dst_ptr given with n_graphs = 0", what);
+  } else {
+    HGIN_ARG_CHECK(src_seg != nullptr, "%s: src_seg NULL", what);
+    HGIN_ARG_CHECK(dst_ptr != nullptr, "%s: dst_ptr NULL", what);
+  }
+  HGIN_ARG_CHECK(n_src >= 1 && n_src < (int64_t(1) << 31), "%s: n_src = %lld must be in [1, 2^31)", what,
+                 (long long)n_src);
+  HGIN_ARG_CHECK(known_rowptr == nullptr || known_col != nullptr, "%s: known_rowptr without known_col", what);
+  HGIN_ARG_CHECK(known_col == nullptr || known_rowptr != nullptr, "%s: known_col without known_rowptr", what);
+  return HGIN_OK;
+}
+
+int link_filt_checks(const char* what, const int64_t* pos, int64_t E, int64_t k, int64_t n_dst, const int32_t* neg_dst,
+                     int64_t m, const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F,
+                     const int32_t* src_seg, const int32_t* dst_ptr, int64_t n_graphs, int64_t n_src,
+                     const int32_t* known_rowptr, const int32_t* known_col) {
+  HGIN_ARG_CHECK(m >= 0 && m < (int64_t(1) << 31), "%s: m = %lld must be >= 0", what, (long long)m);
+  const int rc = m == 0 ? link_common_checks(what, pos, E, k, n_dst, z_src, ld_src, z_dst, ld_dst, F)
+                        : link_given_checks(what, pos, E, k, n_dst, neg_dst, m, z_src, ld_src, z_dst, ld_dst, F);
+  if (rc != HGIN_OK) return rc;
+  return link_filt_window_checks(what, src_seg, dst_ptr, n_graphs, n_src, known_rowptr, known_col);
+}
+
+}  // namespace
+
+extern "C" int hgin_neg_sample_filt(uint64_t seed, uint64_t offset, const int64_t* src, int64_t n_pos, int64_t k,
+                                    int64_t n_dst, const int32_t* src_seg, const int32_t* dst_ptr, int64_t n_graphs,
+                                    int64_t n_src, const int32_t* known_rowptr, const int32_t* known_col, int32_t* out,
+                                    void* stream) {
+  const char* what = "hgin_neg_sample_filt";
+  HGIN_ARG_CHECK(n_pos >= 0 && n_pos < (int64_t(1) << 31), "%s: E = %lld must be in [0, 2^31)", what,
+                 (long long)n_pos);
+  HGIN_ARG_CHECK(k >= 0 && k < (int64_t(1) << 31), "%s: k = %lld must be >= 0", what, (long long)k);
+  HGIN_ARG_CHECK(n_pos * k < (int64_t(1) << 31), "%s: E * k = %lld must be < 2^31", what, (long long)(n_pos * k));
+  HGIN_ARG_CHECK(n_dst >= 1 && n_dst < (int64_t(1) << 31), "%s: n_dst must be in [1, 2^31)", what);
+  const int rc = link_filt_window_checks(what, src_seg, dst_ptr, n_graphs, n_src, known_rowptr, known_col);
+  if (rc != HGIN_OK) return rc;
+  if (n_pos * k == 0) return HGIN_OK;
+  HGIN_ARG_CHECK(src != nullptr, "%s: src NULL", what);
+  HGIN_ARG_CHECK(out != nullptr, "%s: out NULL", what);
+  const int64_t n = n_pos * k;
+  const int64_t grid = ceil_div(n, 256);
+  HGIN_TRACE("k_neg_sample_filt");
+  k_neg_sample_filt<<<(unsigned)(grid < 65536 ? grid : 65536), 256, 0, as_stream(stream)>>>(
+      seed, offset, src, n, (int)k, (uint32_t)n_dst, src_seg, dst_ptr, (int)n_graphs, n_src, known_rowptr, known_col,
+      out);
+  return check_launch(what);
+}
+
+extern "C" int hgin_link_loss_fwd_filt_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64_t seed,
+                                           uint64_t offset, int64_t n_dst, const int32_t* neg_dst, int64_t m,
+                                           const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst,
+                                           int64_t F, float* coef, int64_t* neg, float* loss, void* workspace,
+                                           size_t workspace_bytes, int32_t objective, float param,
+                                           const int32_t* src_seg, const int32_t* dst_ptr, int64_t n_graphs,
+                                           int64_t n_src, const int32_t* known_rowptr, const int32_t* known_col,
+                                           void* stream) {
+  const char* what = "hgin_link_loss_fwd_filt_f32";
+  const int rc = link_filt_checks(what, pos, n_pos, k, n_dst, neg_dst, m, z_src, ld_src, z_dst, ld_dst, F, src_seg,
+                                  dst_ptr, n_graphs, n_src, known_rowptr, known_col);
+  if (rc != HGIN_OK) return rc;
+  HGIN_ARG_CHECK(coef != nullptr, "%s: coef NULL", what);
+  HGIN_ARG_CHECK(neg != nullptr, "%s: neg NULL", what);
+  HGIN_ARG_CHECK(loss != nullptr, "%s: loss NULL", what);
+  HGIN_ARG_CHECK(objective >= kObjBce && objective <= kObjSelfAdv, "%s: objective = %d must be in [0, 3]", what,
+                 (int)objective);
+  HGIN_ARG_CHECK(objective != kObjSoftmax || (std::isfinite(param) && param > 0.0f),
+                 "%s: temperature = %g must be finite and > 0", what, (double)param);
+  HGIN_ARG_CHECK(objective != kObjSelfAdv || (std::isfinite(param) && param >= 0.0f),
+                 "%s: alpha = %g must be finite and >= 0", what, (double)param);
+  if (workspace == nullptr || workspace_bytes < (size_t)kLinkMaxGrid * sizeof(float)) {
+    set_error("%s: workspace %zu bytes < required %zu", what, workspace_bytes, (size_t)kLinkMaxGrid * sizeof(float));
+    return HGIN_E_WORKSPACE;
+  }
+  hipStream_t s = as_stream(stream);
+  const LinkShape sh = link_shape(n_pos, F, z_src, ld_src, z_dst, ld_dst);
+  float* partial = static_cast<float*>(workspace);
+#define HGIN_LINK_FILT(OBJ_)                                                                                          \
+  launch_link_fwd<false, OBJ_, true, true, true>(sh, s, pos, n_pos, (int)k, seed, offset, (uint32_t)n_dst, z_src,     \
+                                                 ld_src, z_dst, ld_dst, (int)F, coef, neg, partial, nullptr, nullptr, \
+                                                 param, neg_dst, (int)m, src_seg, dst_ptr, (int)n_graphs, n_src,      \
+                                                 known_rowptr, known_col)
+  if (objective == kObjBce) HGIN_LINK_FILT(kObjBce);
+  else if (objective == kObjSoftmax) HGIN_LINK_FILT(kObjSoftmax);
+  else if (objective == kObjBpr) HGIN_LINK_FILT(kObjBpr);
+  else HGIN_LINK_FILT(kObjSelfAdv);
+#undef HGIN_LINK_FILT
+  const int rc2 = check_launch(what);
+  if (rc2 != HGIN_OK) return rc2;
+  HGIN_TRACE("k_link_loss_sum");
+  k_link_loss_sum<<<1, 256, 0, s>>>(partial, (int)sh.grid, loss);
+  return check_launch(what);
+}
+
+extern "C" int hgin_link_rank_filt_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64_t seed, uint64_t offset,
+                                       int64_t n_dst, const int32_t* neg_dst, int64_t m, const float* z_src,
+                                       int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F,
+                                       int32_t* n_greater, int32_t* n_equal, const int32_t* src_seg,
+                                       const int32_t* dst_ptr, int64_t n_graphs, int64_t n_src,
+                                       const int32_t* known_rowptr, const int32_t* known_col, void* stream) {
+  const char* what = "hgin_link_rank_filt_f32";
+  const int rc = link_filt_checks(what, pos, n_pos, k, n_dst, neg_dst, m, z_src, ld_src, z_dst, ld_dst, F, src_seg,
+                                  dst_ptr, n_graphs, n_src, known_rowptr, known_col);
+  if (rc != HGIN_OK) return rc;
+  HGIN_ARG_CHECK(n_greater != nullptr, "%s: n_greater NULL", what);
+  HGIN_ARG_CHECK(n_equal != nullptr, "%s: n_equal NULL", what);
+  const LinkShape sh = link_shape(n_pos, F, z_src, ld_src, z_dst, ld_dst);
+  launch_link_fwd<true, kObjBce, true, true, true>(sh, as_stream(stream), pos, n_pos, (int)k, seed, offset,
+                                                   (uint32_t)n_dst, z_src, ld_src, z_dst, ld_dst, (int)F, nullptr,
+                                                   nullptr, nullptr, n_greater, n_equal, 0.0f, neg_dst, (int)m, src_seg,
+                                                   dst_ptr, (int)n_graphs, n_src, known_rowptr, known_col);
   return check_launch(what);
 }
 

@@ -196,6 +196,11 @@ _SIGS = {
                                      _I64, _P], _I32),
     "hgin_link_topk_seg_f32": ([_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _I64, _P, _P, _P, _SZ, _P, _P,
                                 _I64, _P], _I32),
+    "hgin_neg_sample_filt": ([_U64, _U64, _P, _I64, _I64, _I64, _P, _P, _I64, _I64, _P, _P, _P, _P], _I32),
+    "hgin_link_loss_fwd_filt_f32": ([_P, _I64, _I64, _U64, _U64, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _P,
+                                     _P, _SZ, ctypes.c_int32, ctypes.c_float, _P, _P, _I64, _I64, _P, _P, _P], _I32),
+    "hgin_link_rank_filt_f32": ([_P, _I64, _I64, _U64, _U64, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _P, _P,
+                                 _I64, _I64, _P, _P, _P], _I32),
     "hgin_aggregate_long_f32": ([_P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I32, _P, _I64, _P,
                                  _SZ, _P], _I32),
     "hgin_aggregate_long_bf16": ([_P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I32, _P, _I64, _P,
@@ -226,7 +231,7 @@ _SIGS = {
     "hgin_trace_enable": ([_I32], _I32),
     "hgin_trace_read": ([ctypes.c_char_p, _SZ], _SZ),
 }
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 def lib() -> ctypes.CDLL:

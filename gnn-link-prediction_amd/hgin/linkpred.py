@@ -33,6 +33,13 @@ Batches of graphs (A19, not in the reference): ``LinkSegments`` records which gr
 destination row belongs to; the functions above take it as ``segments=`` (mining: ``hard_negatives_seg``) and then draw
 a negative from the positive's own graph and rank / retrieve among that graph's destinations only;
 ``LinkPredictor(graph_local=True)`` builds it from ``graph.batch``.  Without it nothing changes.
+
+Filtered draws (A20, not in the reference): ``negative_edges`` / ``link_loss`` / ``sampled_link_loss`` / ``link_ranks`` /
+``link_metrics`` take ``known=`` (an edge index [2, M], as ``link_full_ranks`` takes it) and then draw every negative
+uniformly from the destinations of its window (all of them, or with ``segments=`` its graph's) that are *not* known
+neighbours of its source: one Philox word mapped onto the r-th non-neighbour, same counters, no rejection loop.  A
+source whose window is all neighbours keeps the unfiltered draw; given negatives (``neg_dst``) are never filtered.
+``LinkPredictor(filter_negatives=True)`` passes the relation's own edges.  Without ``known`` nothing changes.
 """
 from __future__ import annotations
 
@@ -210,6 +217,29 @@ def _check_segments(what: str, segments, n_src: int, n_dst: int, pos: Tensor = N
         pass
 
 
+def _known_shape(what: str, known) -> None:
+    """``known`` is an int64 [2, M] edge index: TypeError / ValueError otherwise.  Looks at the dtype and the shape only,
+    so it runs before any device is needed."""
+    if not isinstance(known, Tensor) or known.dtype != torch.long:
+        got = known.dtype if isinstance(known, Tensor) else type(known).__name__
+        raise TypeError(f"{what}: known must be an int64 edge index [2, M], got {got}")
+    if known.dim() != 2 or int(known.size(0)) != 2:
+        raise ValueError(f"{what}: known must be an edge index [2, M], got {tuple(known.shape)}")
+
+
+def _sample_filt(src: Tensor, k: int, seed: int, offset: int, n_dst: int, segments, csr) -> Tensor:
+    """int32 [E * k]: ``_sample_seg``'s draws (``segments`` None: ``sample_negative_dst``'s) taken from the
+    non-neighbours of each draw's source in ``csr`` = (rowptr, col) by source (include/hgin.h A20)."""
+    E, k = int(src.numel()), int(k)
+    out = torch.empty(E * k, dtype=torch.int32, device=src.device)
+    if E * k:
+        seg = (None, None, 0) if segments is None else (segments.src_seg, segments.dst_ptr, segments.n_graphs)
+        _lib.call("hgin_neg_sample_filt", int(seed) & (2**64 - 1), int(offset) & (2**64 - 1), ops._p(src.contiguous()),
+                  E, k, int(n_dst), ops._p(seg[0]), ops._p(seg[1]), seg[2], int(csr[0].numel()) - 1, ops._p(csr[0]),
+                  ops._p(csr[1]), ops._p(out), ops._stream(out))
+    return out
+
+
 def _sample_seg(src: Tensor, k: int, seed: int, offset: int, segments: LinkSegments) -> Tensor:
     """int32 [E * k]: draw i belongs to positive i // k (source ``src[i // k]``) and has Philox counter offset + i,
     drawn from that source's graph (include/hgin.h A19)."""
@@ -223,17 +253,30 @@ def _sample_seg(src: Tensor, k: int, seed: int, offset: int, segments: LinkSegme
 
 
 def negative_edges(edge_index: Tensor, n_dst: int, k: int, seed: int, offset: int = 0,
-                   neg_dst: Tensor = None, segments: LinkSegments = None) -> Tensor:
+                   neg_dst: Tensor = None, segments: LinkSegments = None, known: Tensor = None) -> Tensor:
     """k corrupted copies of every positive edge: src kept, dst drawn uniformly.  With ``neg_dst``
     (integer [E, m]; include/hgin.h A18) every positive gets k + m copies, destinations [k drawn | m given]; k may be
-    0.  With ``segments`` (a ``LinkSegments``; A19) every draw comes from its positive's own graph."""
+    0.  With ``segments`` (a ``LinkSegments``; A19) every draw comes from its positive's own graph.  With ``known``
+    (an edge index [2, M]; A20) a draw is uniform over the destinations that are not known neighbours of its source
+    (given ones are not filtered); the source row count is ``segments.n_src``, else 1 + the largest source of
+    ``edge_index`` and ``known``."""
     m = _given_shape("negative_edges", neg_dst, edge_index)
+    if known is not None:
+        _known_shape("negative_edges", known)
     if segments is not None:
         _check_segments("negative_edges", segments, None, n_dst, edge_index)
-    ops.require_device(edge_index, what="negative_edges")
+    ops.require_device(edge_index, known, what="negative_edges")
     E = int(edge_index.size(1))
+    csr = None
+    if known is not None:
+        ops.check_edge_index(edge_index)
+        csr = _known_csr(known, None if segments is None else segments.n_src, n_dst, src_of=edge_index)
 
     def draw(n_per):
+        if csr is not None:
+            if n_per < 0 or E * n_per >= 2**31:
+                raise ValueError(f"negative_edges: need k >= 0 and E * k < 2^31 (E = {E}, k = {n_per})")
+            return _sample_filt(edge_index[0], n_per, seed, offset, n_dst, segments, csr)
         if segments is None:
             return sample_negative_dst(E * n_per, n_dst, seed, offset, edge_index.device)
         if n_per < 0 or E * n_per >= 2**31:
@@ -319,14 +362,21 @@ def _objective(what: str, objective, temperature, alpha):
 
 def link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0, objective: str = "bce",
               temperature: float = 1.0, alpha: float = 1.0, neg_dst: Tensor = None,
-              segments: LinkSegments = None) -> Tensor:
+              segments: LinkSegments = None, known: Tensor = None) -> Tensor:
     """The unfused sampled link loss over positives and k uniform negatives per positive: ``objective`` "bce"
     (BCE-with-logits, the default), "softmax", "bpr" or "selfadv" (include/hgin.h A17), as torch ops on the two
     ``dot_decode`` score vectors.  ``neg_dst`` (integer [E, m]) adds m given negatives per positive (A18);
-    ``segments`` (a ``LinkSegments``) draws every negative from its positive's own graph (A19)."""
+    ``segments`` (a ``LinkSegments``) draws every negative from its positive's own graph (A19); ``known`` (an edge
+    index [2, M]) draws it from the destinations that are not known neighbours of its source (A20), through
+    ``negative_edges(known=)``."""
     code, param = _objective("link_loss", objective, temperature, alpha)
     m = _given_shape("link_loss", neg_dst, pos)
-    if segments is not None:
+    if known is not None:
+        _known_shape("link_loss", known)
+        if segments is not None:
+            _check_segments("link_loss", segments, z_src.size(0), z_dst.size(0), pos)
+        neg = negative_edges(pos, z_dst.size(0), k, seed, offset, neg_dst, segments=segments, known=known)
+    elif segments is not None:
         _check_segments("link_loss", segments, z_src.size(0), z_dst.size(0), pos)
         neg = negative_edges(pos, z_dst.size(0), k, seed, offset, neg_dst, segments=segments)
     else:
@@ -398,7 +448,7 @@ def _side_stream(device) -> "torch.cuda.Stream":
 class _SampledLinkLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z_src, z_dst, pos, graph: ops.RelationGraph, k: int, seed: int, offset: int, objective: int = 0,
-                param: float = 0.0, neg_dst: Tensor = None, segments: LinkSegments = None):
+                param: float = 0.0, neg_dst: Tensor = None, segments: LinkSegments = None, known_csr=None):
         E, F, dev = int(pos.size(1)), int(z_src.size(1)), z_src.device
         m = 0 if neg_dst is None else int(neg_dst.size(1))   # A18: k uniform + m given negatives per positive
         K = k + m
@@ -408,7 +458,14 @@ class _SampledLinkLossFn(torch.autograd.Function):
         nbytes = ctypes.c_size_t(0)
         _lib.check(_lib.lib().hgin_link_loss_workspace_size(E, ctypes.byref(nbytes)), "hgin_link_loss_workspace_size")
         ws = ops._workspace(nbytes.value, dev)
-        if segments is not None:   # A19: graph-local draws, given negatives or not; coef / neg as below
+        if known_csr is not None:   # A20: draws from the non-neighbours, segmented or not, given negatives or not
+            seg = (None, None, 0) if segments is None else (segments.src_seg, segments.dst_ptr, segments.n_graphs)
+            _lib.call("hgin_link_loss_fwd_filt_f32", ops._p(pos), E, k, int(seed) & (2**64 - 1),
+                      int(offset) & (2**64 - 1), int(z_dst.size(0)), ops._p(neg_dst), m, ops._p(z_src), z_src.stride(0),
+                      ops._p(z_dst), z_dst.stride(0), F, ops._p(coef), ops._p(neg), ops._p(loss), ops._p(ws),
+                      nbytes.value, objective, param, ops._p(seg[0]), ops._p(seg[1]), seg[2], int(z_src.size(0)),
+                      ops._p(known_csr[0]), ops._p(known_csr[1]), ops._stream(loss))
+        elif segments is not None:   # A19: graph-local draws, given negatives or not; coef / neg as below
             _lib.call("hgin_link_loss_fwd_seg_f32", ops._p(pos), E, k, int(seed) & (2**64 - 1),
                       int(offset) & (2**64 - 1), int(z_dst.size(0)), ops._p(neg_dst), m, ops._p(z_src), z_src.stride(0),
                       ops._p(z_dst), z_dst.stride(0), F, ops._p(coef), ops._p(neg), ops._p(loss), ops._p(ws),
@@ -475,12 +532,12 @@ class _SampledLinkLossFn(torch.autograd.Function):
             _lib.call("hgin_link_loss_bwd_dst_f32", ops._p(csr.rowptr), ops._p(csr.col), ops._p(csr.perm),
                       ops._p(nrow), ops._p(ncol), ops._p(nperm), n_dst, E, ops._p(g), ops._p(coef), ops._p(z_src),
                       z_src.stride(0), F, ops._p(g_dst), g_dst.stride(0), ops._stream(g))
-        return g_src, g_dst, None, None, None, None, None, None, None, None, None
+        return g_src, g_dst, None, None, None, None, None, None, None, None, None, None
 
 
 def sampled_link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0,
                       objective: str = "bce", temperature: float = 1.0, alpha: float = 1.0,
-                      neg_dst: Tensor = None, segments: LinkSegments = None) -> Tensor:
+                      neg_dst: Tensor = None, segments: LinkSegments = None, known: Tensor = None) -> Tensor:
     """``link_loss`` in fused form (include/hgin.h A13 / A17): the same pairs (``negative_edges(pos, n_dst, k, seed,
     offset)``) and the same loss, one forward pass that draws the negatives in the kernel and reads every source
     row once, and a deterministic store-and-sum backward (static CSC / CSR of ``pos`` + one sort of the step's
@@ -491,8 +548,22 @@ def sampled_link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: i
     positive's k drawn ones (include/hgin.h A18): K = k + m takes k's place in every weight and normaliser, k may be
     0, and a given destination contributes exactly what the same destination would as a draw.  ``segments`` (a
     ``LinkSegments``; include/hgin.h A19) draws every negative from its positive's own graph, at the same Philox
-    counters; with one graph the result is bit for bit the unsegmented one.  Returns a scalar; fp32 embeddings only."""
+    counters; with one graph the result is bit for bit the unsegmented one.  ``known`` (an int64 edge index [2, M] on the
+    device; include/hgin.h A20; its CSR is built and range-checked once per tensor version, as ``link_full_ranks``
+    builds it) draws every negative uniformly from the destinations of its window (all of them, or its graph's) that
+    are not known neighbours of its source, at the same counters: a source without known edges keeps today's draw bit
+    for bit, a source whose window is all neighbours keeps the unfiltered draw (it has no true negative), and
+    ``neg_dst`` is never filtered.  Returns a scalar; fp32 embeddings only."""
     code, param = _objective("sampled_link_loss", objective, temperature, alpha)
+    if known is not None:
+        _known_shape("sampled_link_loss", known)
+        ops_ = _link_operands("sampled_link_loss", z_src, z_dst, pos, k, neg_dst, segments)
+        ops.require_device(known, what="sampled_link_loss")
+        z_src, z_dst, pos, graph, _, k = ops_[:6]
+        given = ops_[6] if len(ops_) > 6 else None
+        csr = _known_csr(known, int(z_src.size(0)), int(z_dst.size(0)))
+        return _SampledLinkLossFn.apply(z_src, z_dst, pos, graph, k, int(seed), int(offset), code, param, given,
+                                        segments, csr)
     if segments is not None:
         ops_ = _link_operands("sampled_link_loss", z_src, z_dst, pos, k, neg_dst, segments)
         z_src, z_dst, pos, graph, _, k = ops_[:6]
@@ -507,12 +578,16 @@ def sampled_link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: i
 
 
 def link_ranks(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0, neg_dst: Tensor = None,
-               segments: LinkSegments = None):
+               segments: LinkSegments = None, known: Tensor = None):
     """(n_greater, n_equal), int32 [E]: how many of each positive's k sampled negatives (the draws of
     ``sampled_link_loss``) score above / exactly equal to it (include/hgin.h A14); with ``neg_dst`` (integer [E, m],
     e.g. a fixed evaluation set; A18) the counts cover the k draws and the m given negatives, and k may be 0.  With
-    ``segments`` (a ``LinkSegments``; A19) the draws come from each positive's own graph.  No gradient."""
+    ``segments`` (a ``LinkSegments``; A19) the draws come from each positive's own graph.  With ``known`` (an edge
+    index [2, M]; A20) the draws are ``sampled_link_loss(known=)``'s: no known neighbour of the source is counted as a
+    beaten or lost candidate (unless its window holds nothing else).  No gradient."""
     given = None
+    if known is not None:
+        _known_shape("link_ranks", known)
     if neg_dst is None:
         z_src, z_dst, pos, _, E, k = _link_operands("link_ranks", z_src, z_dst, pos, k, None, segments)
     else:
@@ -520,6 +595,16 @@ def link_ranks(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, off
     z_src, z_dst = z_src.detach(), z_dst.detach()
     n_gt = torch.empty(E, dtype=torch.int32, device=z_src.device)
     n_eq = torch.empty(E, dtype=torch.int32, device=z_src.device)
+    if known is not None:
+        ops.require_device(known, what="link_ranks")
+        csr = _known_csr(known, int(z_src.size(0)), int(z_dst.size(0)))
+        seg = (None, None, 0) if segments is None else (segments.src_seg, segments.dst_ptr, segments.n_graphs)
+        _lib.call("hgin_link_rank_filt_f32", ops._p(pos), E, k, int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
+                  int(z_dst.size(0)), ops._p(given), 0 if given is None else int(given.size(1)), ops._p(z_src),
+                  z_src.stride(0), ops._p(z_dst), z_dst.stride(0), int(z_src.size(1)), ops._p(n_gt), ops._p(n_eq),
+                  ops._p(seg[0]), ops._p(seg[1]), seg[2], int(z_src.size(0)), ops._p(csr[0]), ops._p(csr[1]),
+                  ops._stream(n_gt))
+        return n_gt, n_eq
     if segments is not None:
         _lib.call("hgin_link_rank_seg_f32", ops._p(pos), E, k, int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
                   int(z_dst.size(0)), ops._p(given), 0 if given is None else int(given.size(1)), ops._p(z_src),
@@ -551,11 +636,16 @@ def metrics_from_ranks(n_greater: Tensor, n_equal: Tensor, k: int) -> dict:
 
 
 def link_metrics(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, offset: int = 0,
-                 neg_dst: Tensor = None, segments: LinkSegments = None) -> dict:
+                 neg_dst: Tensor = None, segments: LinkSegments = None, known: Tensor = None) -> dict:
     """auc / mrr / hits@1 / hits@3 / hits@10 of the positives against k sampled negatives each, as device scalars
     (float64): the ranking kernel + a few reductions over [E]; no host sync before the caller reads a value.  With
     ``neg_dst`` (integer [E, m]; A18) against the k draws and the m given negatives (the set's one-off range check
-    aside).  ``segments`` (a ``LinkSegments``; A19): the draws come from each positive's own graph."""
+    aside).  ``segments`` (a ``LinkSegments``; A19): the draws come from each positive's own graph.  ``known``
+    (an edge index [2, M]; A20): the draws leave out the known neighbours of each positive's source, as the full
+    metrics' ``known`` leaves them out of the candidates."""
+    if known is not None:
+        n_gt, n_eq = link_ranks(z_src, z_dst, pos, k, seed, offset, neg_dst, segments=segments, known=known)
+        return metrics_from_ranks(n_gt, n_eq, int(k) + (0 if neg_dst is None else int(neg_dst.size(1))))
     if segments is not None:
         n_gt, n_eq = link_ranks(z_src, z_dst, pos, k, seed, offset, neg_dst, segments=segments)
         return metrics_from_ranks(n_gt, n_eq, int(k) + (0 if neg_dst is None else int(neg_dst.size(1))))
@@ -569,16 +659,36 @@ def link_metrics(z_src: Tensor, z_dst: Tensor, pos: Tensor, k: int, seed: int, o
 # ---------------------------------------------------------------------------------------------------
 # A15: full-candidate filtered ranking (NOT IN REFERENCE)
 # ---------------------------------------------------------------------------------------------------
-def _known_csr(known: Tensor, n_src: int, n_dst: int):
+def _known_csr(known: Tensor, n_src: int, n_dst: int, src_of: Tensor = None):
     """(rowptr int32 [n_src + 1], col int32) of ``known`` by source: columns sorted within a row, duplicates removed.
-    Built (and range-checked, one host sync) once per tensor version and cached on the tensor."""
-    key = (int(n_src), int(n_dst))
+    Built (and range-checked, one host sync) once per tensor version and cached on the tensor.  ``n_src`` None (a
+    caller without a row count: ``negative_edges``): 1 + the largest source over ``known`` and the edge index
+    ``src_of`` (one more sync inside the same cached build), cached per (``src_of`` tensor, its version)."""
     cache = getattr(known, "_hgin_known_csr", None)
     ver = known._version
-    if cache is not None and cache[0] == ver and key in cache[1]:
-        return cache[1][key]
+    if n_src is None:
+        key = ("auto", int(n_dst))
+        hit = cache[1].get(key) if cache is not None and cache[0] == ver else None
+        if hit is not None and hit[0]() is src_of and hit[1] == src_of._version:
+            return hit[2]
+    else:
+        key = (int(n_src), int(n_dst))
+        if cache is not None and cache[0] == ver and key in cache[1]:
+            return cache[1][key]
     ops.check_edge_index(known)
     dev = known.device
+    if n_src is None:
+        if known.device != src_of.device:
+            raise ValueError(f"known is on {known.device}, the positives on {src_of.device}")
+        tops = [t[0].amax() for t in (known, src_of) if t.size(1)]
+        n_src = 1 + max(int(torch.stack(tops).amax()) if tops else 0, 0)
+        if n_src >= 2**31:
+            raise IndexError("known: src index out of range [0, 2^31)")
+        out = _known_csr(known, n_src, n_dst)
+        cache = getattr(known, "_hgin_known_csr", None)
+        if cache is not None and cache[0] == ver:
+            cache[1][key] = (weakref.ref(src_of), src_of._version, out)
+        return out
     if known.size(1):
         lo, hi = known.amin(1), known.amax(1)
         bounds = torch.stack([lo[0], hi[0], lo[1], hi[1]]).tolist()
@@ -738,7 +848,8 @@ def hard_negatives(z_src: Tensor, z_dst: Tensor, pos: Tensor, m: int, known: Ten
     (score descending, index ascending): ``link_topk`` on the unique sources of ``pos``, gathered back per positive.
     A source with fewer than m such destinations leaves padded slots; slot (e, j) is then filled with the uniform
     draw ``sample_negative_dst(E * m, n_dst, seed, offset)[e * m + j]``, which is not filtered and may be a known
-    edge.  1 <= m <= 128.  No gradient.  ``hard_negatives_seg`` is the graph-local form."""
+    edge (the filtered draws of include/hgin.h A20 do not reach this fill, and the parameter list stays as it is).
+    1 <= m <= 128.  No gradient.  ``hard_negatives_seg`` is the graph-local form."""
     return _hard_negatives("hard_negatives", z_src, z_dst, pos, m, known, seed, offset, None)
 
 
@@ -747,7 +858,8 @@ def hard_negatives_seg(z_src: Tensor, z_dst: Tensor, pos: Tensor, m: int, segmen
     """``hard_negatives`` inside each positive's own graph (``segments``: a ``LinkSegments``; include/hgin.h A19): the
     mining goes through the segmented ``link_topk`` and the padded slots take the segmented draws of the same stream
     (counter offset + e * m + j), so every entry lies in its positive's graph.  A function of its own, and not a
-    ``segments=`` on ``hard_negatives``, whose parameter list is a fixed part of the public surface."""
+    ``segments=`` on ``hard_negatives``, whose parameter list is a fixed part of the public surface.  The fill is
+    unfiltered here too (A20 leaves it alone)."""
     if not isinstance(segments, LinkSegments):
         raise TypeError(f"hard_negatives_seg: segments must be a LinkSegments, got {type(segments).__name__}")
     return _hard_negatives("hard_negatives_seg", z_src, z_dst, pos, m, known, seed, offset, segments)
@@ -791,10 +903,16 @@ class LinkPredictor:
     ``graph_local`` = True is for a collated batch of independent graphs (``hgin.data.collate``, ``component_graph``):
     ``LinkSegments.of(graph, relation)`` is built once per graph object and passed to ``loss``, ``mine``, ``metrics``,
     ``full_metrics`` and ``predict``, so negatives, candidates and proposals stay inside each positive's / source's own
-    graph (include/hgin.h A19).  The default treats the destinations as one pool, as before."""
+    graph (include/hgin.h A19).  The default treats the destinations as one pool, as before.
+
+    ``filter_negatives`` = True draws the uniform negatives of ``loss`` and ``metrics`` from each source's
+    non-neighbours (include/hgin.h A20): ``known`` = the relation's edges in the graph, or what the call's own
+    ``known=`` gives (train + valid + test edges for held-out positives).  It composes with ``graph_local``, ``hard``
+    (whose mined set is filtered by the relation's edges already; its padding fill is not) and every objective."""
 
     def __init__(self, model, relation, k: int, seed: int, objective: str = "bce", temperature: float = 1.0,
-                 alpha: float = 1.0, hard: int = 0, mine_every: int = 1, graph_local: bool = False):
+                 alpha: float = 1.0, hard: int = 0, mine_every: int = 1, graph_local: bool = False,
+                 filter_negatives: bool = False):
         if not hasattr(model, "encode"):
             raise TypeError("LinkPredictor: the model has no encode(x_dict, edge_index_dict)")
         _objective("LinkPredictor", objective, temperature, alpha)
@@ -812,6 +930,7 @@ class LinkPredictor:
         self._mined_for = None
         self.graph_local = bool(graph_local)
         self._segments = None     # (graph, its LinkSegments) of the last graph seen with graph_local
+        self.filter_negatives = bool(filter_negatives)
 
     def _seg_kw(self, graph) -> dict:
         """{} by default (every call below is then exactly the unsegmented one), {"segments": ...} with graph_local."""
@@ -820,6 +939,13 @@ class LinkPredictor:
         if self._segments is None or self._segments[0] is not graph:
             self._segments = (graph, LinkSegments.of(graph, self.relation))
         return {"segments": self._segments[1]}
+
+    def _known_kw(self, graph, known) -> dict:
+        """{} by default (the calls below then carry no ``known`` keyword at all); {"known": ...} when the call gives
+        one or ``filter_negatives`` is set (then the relation's own edges)."""
+        if known is not None:
+            return {"known": known}
+        return {"known": graph.edge_index[self.relation]} if self.filter_negatives else {}
 
     def _pos(self, graph, pos):
         return graph.edge_index[self.relation] if pos is None else pos
@@ -837,23 +963,25 @@ class LinkPredictor:
         self._mined_for = pos
         return self.neg_dst
 
-    def loss(self, graph, pos: Tensor = None, step: int = 0) -> Tensor:
+    def loss(self, graph, pos: Tensor = None, step: int = 0, known: Tensor = None) -> Tensor:
         """The sampled loss of ``pos`` (default: the relation's own edges); step s draws the negatives at
         offset s * E * k, so every step sees fresh ones.  With ``hard`` > 0 the mined set joins them; it is mined
         again from this step's embeddings (detached; no second encode) when ``mine_every`` > 0 divides the step, or
-        when there is none for this ``pos`` yet (padded slots: draws at offset s * E * hard)."""
+        when there is none for this ``pos`` yet (padded slots: draws at offset s * E * hard).  ``known`` (an edge
+        index; default with ``filter_negatives``: the relation's own edges) filters the uniform draws (A20)."""
         pos = self._pos(graph, pos)
         z = self.model.encode(graph.x_dict(), graph.edge_index_dict())
         offset = int(step) * int(pos.size(1)) * self.k
         if self.hard == 0:
             return sampled_link_loss(z[self.relation[0]], z[self.relation[2]], pos, self.k, self.seed, offset,
-                                     self.objective, self.temperature, self.alpha, **self._seg_kw(graph))
+                                     self.objective, self.temperature, self.alpha, **self._seg_kw(graph),
+                                     **self._known_kw(graph, known))
         if self.neg_dst is None or self._mined_for is not pos or \
                 (self.mine_every > 0 and int(step) % self.mine_every == 0):
             self._mine(z, graph, pos, None, int(step) * int(pos.size(1)) * self.hard)
         return sampled_link_loss(z[self.relation[0]], z[self.relation[2]], pos, self.k, self.seed, offset,
                                  self.objective, self.temperature, self.alpha, neg_dst=self.neg_dst,
-                                 **self._seg_kw(graph))
+                                 **self._seg_kw(graph), **self._known_kw(graph, known))
 
     def mine(self, graph, pos: Tensor = None, known: Tensor = None) -> Tensor:
         """Mine ``self.neg_dst`` now, from an eval-mode encode without gradients (the mode is restored), as
@@ -871,9 +999,10 @@ class LinkPredictor:
         finally:
             self.model.train(was_training)
 
-    def metrics(self, graph, pos: Tensor = None, neg_dst: Tensor = None) -> dict:
+    def metrics(self, graph, pos: Tensor = None, neg_dst: Tensor = None, known: Tensor = None) -> dict:
         """``link_metrics`` of the model's embeddings in eval mode, without gradients (the mode is restored);
-        ``neg_dst`` (integer [E, m]) is an evaluation set ranked along with the k uniform draws."""
+        ``neg_dst`` (integer [E, m]) is an evaluation set ranked along with the k uniform draws.  ``known`` (an edge
+        index; default with ``filter_negatives``: the relation's own edges) filters the uniform draws (A20)."""
         pos = self._pos(graph, pos)
         was_training = self.model.training
         self.model.eval()
@@ -882,9 +1011,9 @@ class LinkPredictor:
                 z = self.model.encode(graph.x_dict(), graph.edge_index_dict())
                 if neg_dst is not None:
                     return link_metrics(z[self.relation[0]], z[self.relation[2]], pos, self.k, self.seed,
-                                        neg_dst=neg_dst, **self._seg_kw(graph))
+                                        neg_dst=neg_dst, **self._seg_kw(graph), **self._known_kw(graph, known))
                 return link_metrics(z[self.relation[0]], z[self.relation[2]], pos, self.k, self.seed,
-                                    **self._seg_kw(graph))
+                                    **self._seg_kw(graph), **self._known_kw(graph, known))
         finally:
             self.model.train(was_training)
 

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define HGIN_ABI_VERSION 14
+#define HGIN_ABI_VERSION 15
 
 #define HGIN_OK 0
 #define HGIN_E_ARG (-1)        /* bad size / null pointer / unsupported combination */
@@ -656,6 +656,59 @@ int hgin_link_topk_seg_f32(const int64_t* src, int64_t n_query, int64_t n_src, i
                            const int32_t* known_col, int64_t k, int32_t* top_idx, float* top_score, void* ws,
                            size_t ws_bytes, const int32_t* src_seg, const int32_t* dst_ptr, int64_t n_graphs,
                            void* stream);
+
+/* ---- A20: sampled negatives drawn from each source's non-neighbours (NOT IN REFERENCE; build-defined, ABI 15) ------
+ * The draws of A10 / A13 / A14 / A17 / A18 / A19 are uniform over a window of destinations and may name a true edge.
+ * The *_filt entry points draw uniformly over the window minus the source's known neighbours instead, from the same
+ * Philox word: no rejection, no retry, draw i still has counter offset + i.
+ *   Window of positive e (source s): [lo, lo + n) = [0, n_dst) without a segmentation (n_graphs = 0, src_seg = dst_ptr
+ *     = NULL: one pool), A19's segment of s otherwise.
+ *   Known row of s: known_col[known_rowptr[s] .. known_rowptr[s + 1]), the CSR by source of A15 / A16 (known_rowptr
+ *     int32 [n_src + 1], known_col int32); the caller guarantees columns strictly increasing within a row and inside
+ *     [0, n_dst).  c_0 < ... < c_{d-1} = the row's columns inside the window, found by two lower bounds on the row (known
+ *     edges that leave the graph are ignored, as A19 ignores them for ranking); f = n - d free destinations.
+ *   Draw of slot t = 1 .. k: counter c = offset + e k + t - 1, word w = block(c >> 2)[c & 3], key = seed, as A13.
+ *     f == 0 (every destination of the window is a neighbour; such a source has no true negative):
+ *       draw = lo + hi32(w * n), the unfiltered draw, which is then a known edge.
+ *     otherwise r = hi32(w * f), j = the smallest index with (c_j - lo) - j > r (d if there is none; the sequence
+ *       (c_i - lo) - i is non-decreasing, so j comes from a binary search), draw = lo + r + j: the r-th element,
+ *       0-based, of the window minus the neighbours.  Exactly uniform over the complement (as uniform as A10 is over
+ *       [0, n_dst)), deterministic.
+ *     An empty row gives f = n, j = 0: bit for bit A13's draw (one pool) or A19's (segmented).
+ *   Hand case: window [10, 16), known columns {11, 12, 15}: free = {10, 13, 14}, f = 3.  seed 0, offset 0 gives
+ *     Random123's known-answer words 6627e8d5 e169c58d bc57ac4c 9b00dbd8, so r = 1, 2, 2, 1 and the draws are
+ *     13, 14, 14, 13.
+ * Given negatives (neg_dst, A18) are the caller's choice and are not filtered.  known need not contain the positives;
+ * what is not in it can be drawn.  known_rowptr = known_col = NULL: no known edges (the *_seg / A18 bits).
+ * A row that breaks the guarantee (unsorted, repeated or out-of-range columns) makes the draw unspecified; it still
+ * lands inside the window clamped to [0, n_dst) and nothing is read outside the row: s is clamped into [0, n_src), a
+ * row end below its start counts as empty, d > n counts as f = 0, and a drawn id is kept below n_dst as A19 keeps it.
+ * Everything downstream is A13 / A14 / A17 / A18 / A19 unchanged: scores, loss terms, summation order, the coef / neg
+ * layout, both backward entry points; a filtered draw of destination c contributes the bits c contributes as a given
+ * negative.  In k_link_fwd the filter is one more compile-time flag, instantiated in its given + segmented form only
+ * (m = 0 and n_graphs = 0 are run-time cases; HGIN_TRACE tag: the *_seg tag of what the call uses, then ",FILT"): row
+ * bounds, window clip, d and f once per positive, one search per drawn pair (the searches of a batch of four advance
+ * together; given pairs are not searched).  The unfiltered entry points, their instantiations and bits are unchanged.
+ *   hgin_neg_sample_filt: hgin_neg_sample_seg's (src, n_pos, k) form plus n_dst (the pool when n_graphs = 0).
+ *   hgin_link_loss_fwd_filt_f32: hgin_link_loss_fwd_seg_f32's arguments plus n_src / known_rowptr / known_col; neg_dst =
+ *     NULL with m = 0 allowed (then k >= 1); every objective.
+ *   hgin_link_rank_filt_f32: hgin_link_rank_seg_f32's likewise.
+ * Status: the *_seg ranges and codes, with n_graphs = 0 allowed when src_seg = dst_ptr = NULL; HGIN_E_ARG before any
+ * launch for n_graphs = 0 with a segmentation pointer, n_src < 1, known_rowptr without known_col or the reverse. */
+int hgin_neg_sample_filt(uint64_t seed, uint64_t offset, const int64_t* src, int64_t n_pos, int64_t k, int64_t n_dst,
+                         const int32_t* src_seg, const int32_t* dst_ptr, int64_t n_graphs, int64_t n_src,
+                         const int32_t* known_rowptr, const int32_t* known_col, int32_t* out, void* stream);
+int hgin_link_loss_fwd_filt_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64_t seed, uint64_t offset,
+                                int64_t n_dst, const int32_t* neg_dst, int64_t m, const float* z_src, int64_t ld_src,
+                                const float* z_dst, int64_t ld_dst, int64_t F, float* coef, int64_t* neg, float* loss,
+                                void* workspace, size_t workspace_bytes, int32_t objective, float param,
+                                const int32_t* src_seg, const int32_t* dst_ptr, int64_t n_graphs, int64_t n_src,
+                                const int32_t* known_rowptr, const int32_t* known_col, void* stream);
+int hgin_link_rank_filt_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64_t seed, uint64_t offset,
+                            int64_t n_dst, const int32_t* neg_dst, int64_t m, const float* z_src, int64_t ld_src,
+                            const float* z_dst, int64_t ld_dst, int64_t F, int32_t* n_greater, int32_t* n_equal,
+                            const int32_t* src_seg, const int32_t* dst_ptr, int64_t n_graphs, int64_t n_src,
+                            const int32_t* known_rowptr, const int32_t* known_col, void* stream);
 
 /* ---- F4 widening: HetroGAT's graph attention (models.py:380-506, PyG 2.0.2 GATConv) ---------------------------
  * x_s / x_d: projected source / destination features [N, H * C] (row stride ld*), edges = the relation after

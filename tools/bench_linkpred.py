@@ -28,10 +28,15 @@ from the first ``--mine-sources`` source rows (the random-given pair keeps the s
 the positives sorted by graph and times the fused step with ``segments=`` against the same step without it, on the
 same tensors, alternating in one run.
 
+``--filter`` (include/hgin.h A20; composes with ``--graphs``) times the fused forward + backward of the loss with
+``known`` = the positives (every draw taken from its source's non-neighbours) against the same call without it, on the
+same tensors, alternating in one run; with ``--graphs G`` both calls carry ``segments=``.
+
     python tools/bench_linkpred.py --out profiles/linkpred/linkpred_bench.json
     python tools/bench_linkpred.py --k 1 --hard 4 --out profiles/linkpred/linkhard_bench.json
     python tools/bench_linkpred.py --objective all --out profiles/linkpred/linkobj_bench.json
     python tools/bench_linkpred.py --graphs 8      # profiles/linkseg/linkrank_seg_bench.json, "loss_step"
+    python tools/bench_linkpred.py --filter [--graphs 8]      # profiles/linkfilt/linkfilt_bench.json
     python tools/bench_linkpred.py --configs cfg1 --scale 0.1 --k 1      # a tiny run
 """
 import argparse
@@ -328,12 +333,75 @@ def run_graphs(torch, shape, graphs, repeats, warmup, target_ms, seed=1234):
     return out
 
 
+def run_filter(torch, shape, graphs, repeats, warmup, target_ms, seed=1234):
+    """The ``--filter`` measurements of one shape: the fused forward + backward step with ``known`` = the positives
+    against the same step without it, on the same tensors (cut into ``graphs`` equal graphs and carrying ``segments=``
+    when graphs > 1), the paths alternating in one run.  Also recorded: the known rows' lengths and the share of the
+    unfiltered step's draws that are known edges of their source."""
+    from hgin.linkpred import LinkSegments, _known_csr, sampled_link_loss
+    dev = "cuda"
+    n_src, n_dst, E, F, k = (shape[x] for x in ("n_src", "n_dst", "E", "F", "k"))
+    g = torch.Generator(device=dev).manual_seed(seed)
+    kw = {}
+    if graphs > 1:
+        pos, batch_src, batch_dst = split_graphs(n_src, n_dst, E, graphs, seed, dev)
+        kw["segments"] = LinkSegments(batch_src, batch_dst, graphs)
+    else:
+        pos = torch.stack([torch.randint(0, n_src, (E,), generator=g, device=dev),
+                           torch.randint(0, n_dst, (E,), generator=g, device=dev)])
+    z_src = (torch.randn(n_src, F, generator=g, device=dev) * 0.1).requires_grad_(True)
+    z_dst = (torch.randn(n_dst, F, generator=g, device=dev) * 0.1).requires_grad_(True)
+
+    def step_of(extra):
+        def fn(step):
+            z_src.grad = z_dst.grad = None
+            sampled_link_loss(z_src, z_dst, pos, k, seed, step * E * k, **kw, **extra).backward()
+        return fn
+
+    paths = {"unfiltered": step_of({}), "filtered": step_of({"known": pos})}
+    for s in range(warmup):
+        for fn in paths.values():
+            fn(s)
+    torch.cuda.synchronize()
+    inner = {name: _inner_for(torch, fn, target_ms) for name, fn in paths.items()}
+    times, step = {name: [] for name in paths}, warmup
+    for _ in range(repeats):      # the paths alternate
+        for name, fn in paths.items():
+            times[name].append(_timed(torch, fn, inner[name], step))
+        step += max(inner.values())
+    rowptr, _ = _known_csr(pos, n_src, n_dst)
+    deg = (rowptr[1:] - rowptr[:-1])[pos[0]].double()
+    plain = sampled_link_loss(z_src, z_dst, pos, k, seed, 0, **kw)
+    filt = sampled_link_loss(z_src, z_dst, pos, k, seed, 0, known=pos, **kw)
+    edge_keys = torch.unique(pos[0] * n_dst + pos[1])
+
+    def known_share(loss):
+        neg = loss.grad_fn.saved_tensors[1]
+        return float(torch.isin(neg[0] * n_dst + neg[1], edge_keys).double().mean())
+
+    out = dict(shape, graphs=graphs, known="the positives", known_row_mean=float(deg.mean()),
+               known_row_max=int(deg.max()), unfiltered_draws_known_share=known_share(plain),
+               filtered_draws_known_share=known_share(filt))
+    for name in paths:
+        out[name] = dict(_stats(times[name]), inner=inner[name])
+    a, b = out["filtered"], out["unfiltered"]
+    out["filtered_over_unfiltered"] = a["median_ms"] / b["median_ms"]
+    out["filtered_within_spread_of_unfiltered"] = a["min_ms"] <= b["max_ms"] and b["min_ms"] <= a["max_ms"]
+    z_src.grad = z_dst.grad = None
+    del z_src, z_dst, pos
+    torch.cuda.empty_cache()
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--configs", default="cfg2,cfg3")
     ap.add_argument("--graphs", type=int, default=1,
                     help="cut every shape into G equal graphs, positives sorted by graph, and time the fused step with "
                          "segments= against the same step without (include/hgin.h A19); 1: today's measurements")
+    ap.add_argument("--filter", action="store_true",
+                    help="time the fused step with known = the positives against the same step without it "
+                         "(include/hgin.h A20); composes with --graphs")
     ap.add_argument("--k", default="1,4")
     ap.add_argument("--scale", type=float, default=1.0, help="multiply every node / edge count (tiny runs)")
     ap.add_argument("--repeats", type=int, default=7)
@@ -351,6 +419,8 @@ def main(argv=None) -> int:
         ap.error("--hard must be in [1, 128]")
     if args.graphs < 1:
         ap.error("--graphs must be at least 1")
+    if args.filter and (args.hard is not None or args.objective != "bce"):
+        ap.error("--filter composes with --graphs only")
     objectives = objectives_of(args.objective)
     shapes = plan(args.configs.split(","), [int(v) for v in args.k.split(",")], args.scale)
     for s in shapes:
@@ -362,6 +432,16 @@ def main(argv=None) -> int:
         return 2
     from hgin import _lib
     _lib.lib()
+    if args.filter:
+        results = [run_filter(torch, s, args.graphs, args.repeats, args.warmup, args.target_ms) for s in shapes]
+        doc = {"tool": "tools/bench_linkpred.py", "device": torch.cuda.get_device_name(0), "repeats": args.repeats,
+               "warmup": args.warmup, "filter": True, "graphs": args.graphs, "shapes": results}
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(json.dumps(doc, indent=1) + "\n")
+        print(json.dumps(doc))
+        return 0
     if args.graphs > 1:
         results = [run_graphs(torch, s, args.graphs, args.repeats, args.warmup, args.target_ms) for s in shapes]
         doc = {"tool": "tools/bench_linkpred.py", "device": torch.cuda.get_device_name(0), "repeats": args.repeats,
