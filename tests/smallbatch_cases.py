@@ -1,5 +1,6 @@
 """Shared case builder of the fused small-batch step's shape tests (tests/test_smallbatch_shapes_host.py,
-tests/test_gpu_smallbatch_edges.py; the oracle comparison also serves tests/test_gpu_smallbatch.py): small
+tests/test_gpu_smallbatch_edges.py; the oracle comparison also serves tests/test_gpu_smallbatch.py, the host dropout
+masks tests/test_gpu_dropmask.py and the two files' dropout tests): small
 deterministic graphs whose row counts and degrees are prescribed exactly, a Python mirror of the staging arithmetic of
 csrc/hgin_smallbatch.hip's weight-gradient loops (so that a test can assert that its case reaches the loop iteration it
 claims to reach), the host collation pinned to oracle/collate_np.py, and the comparison of one fused step with the CPU
@@ -246,6 +247,138 @@ def check_buffers(model, ref) -> None:
         else:
             assert torch.allclose(u.cpu().double(), v.double(), rtol=1e-5, atol=1e-6), \
                 (n, float((u.cpu() - v).abs().max()))
+
+
+# ---- dropout: the step's masks restated on the host ----------------------------------------------------------------
+
+def store_graphs(n: int, seed: int) -> List[HeteroGraph]:
+    """``n`` cfg1 graphs scaled by factors drawn in [0.5, 1.5) (tests/test_gpu_smallbatch.py's ``_store``, on the
+    host): what a test hands to GraphStore.build(..., normalize=True)."""
+    import numpy as np
+
+    from hgin.data import scaled_config, synthetic_graph
+    rng = np.random.default_rng(seed)
+    cfg = CONFIGS["cfg1"]
+    return [synthetic_graph(scaled_config(cfg, float(rng.uniform(0.5, 1.5)), name=f"g{i}"), seed=seed * 100 + i)
+            for i in range(n)]
+
+
+def store_host_batch(graphs: Sequence[HeteroGraph], ids) -> HeteroGraph:
+    """The batch ``ids`` of the normalised store of ``graphs`` formed on the host alone (hgin.data.collate, then
+    dataset.py:33-58's per-column normalisation, which is row by row what the store applies to all its rows)."""
+    from hgin.data import collate
+    from hgin.store import normalize_reference
+    b = collate([graphs[i] for i in ids])
+    return HeteroGraph(normalize_reference(b.x), b.edge_index, b.y, b.batch)
+
+
+class HostDropout:
+    """``torch.nn.functional.dropout`` replaced by the fused step's own masks, computed on the host by
+    oracle/dropout_np.py from (seed, step counter, layer, type, element) alone: nothing here reads an output of the
+    step.  The oracle calls F.dropout once per node type after every layer (models.py:358-359); the type is told by the
+    row count (the three must differ), the layer by counting the calls per type.  ``out[(l, t)]`` keeps what the
+    oracle's dropout returned for layer l and type index t (0 / 1 / 2 = path / link / node), detached.
+
+    One oracle forward per ``at(ctr)``: it sets the step counter whose masks apply and restarts the layer count."""
+
+    def __init__(self, seed: int, p: float, rows_by_type: Dict[str, int], H: int):
+        rows = [rows_by_type[t] for t in TYPES]
+        assert len(set(rows)) == 3, rows
+        self.seed, self.p, self.rows, self.H = int(seed), float(p), rows, int(H)
+        self.ctr, self.calls, self.out = None, {}, {}
+
+    def at(self, ctr: int, rows_by_type: Optional[Dict[str, int]] = None) -> "HostDropout":
+        if rows_by_type is not None:   # (another batch of the same capture)
+            self.rows = [rows_by_type[t] for t in TYPES]
+            assert len(set(self.rows)) == 3, self.rows
+        self.ctr, self.calls, self.out = int(ctr), {}, {}
+        return self
+
+    def keep(self, l: int, ti: int, ctr: Optional[int] = None) -> torch.Tensor:
+        """[rows of type ti][H] bool: the elements of layer l's type-ti output that the step ``ctr`` keeps."""
+        from oracle import dropout_np
+        return torch.from_numpy(dropout_np.keep_mask(self.seed, self.ctr if ctr is None else ctr, l, ti,
+                                                     self.rows[ti], self.H, self.p))
+
+    def __call__(self, x, p=0.5, training=True, inplace=False):
+        from oracle import dropout_np
+        assert training and not inplace and p == self.p and x.shape[1] == self.H and self.ctr is not None
+        ti = self.rows.index(x.shape[0])
+        l = self.calls.get(ti, 0)
+        self.calls[ti] = l + 1
+        y = x * (self.keep(l, ti).to(x.dtype) * dropout_np.drop_scale(self.p))
+        self.out[(l, ti)] = y.detach().clone()
+        return y
+
+
+def host_dropout(monkeypatch, seed: int, ctr: int, p: float, rows_by_type: Dict[str, int], H: int) -> HostDropout:
+    """Patch torch.nn.functional.dropout with the host masks of the step ``ctr`` (HostDropout) for the test's duration."""
+    hd = HostDropout(seed, p, rows_by_type, H).at(ctr)
+    monkeypatch.setattr(torch.nn.functional, "dropout", hd)
+    return hd
+
+
+def act_blocks(step, rows_by_type: Dict[str, int]) -> Dict[Tuple[int, int], torch.Tensor]:
+    """(l, type index) -> the valid rows [n_t][H] of the step's layer outputs (``step.act``), on the host."""
+    a, act = step.args, step.act.detach().cpu()
+    out = {}
+    for l in range(a.L):
+        for ti, t in enumerate(TYPES):
+            o, n = a.act_off[l][ti], rows_by_type[t]
+            out[(l, ti)] = act[o:o + n * a.H].view(n, a.H).clone()
+    return out
+
+
+def check_dropped_zero(blocks, hd: HostDropout, ctr: Optional[int] = None) -> None:
+    """Every element that the host mask of the step drops is an exact 0 in the step's layer outputs (no cap: one
+    surviving element fails).  Kept elements may be 0 too (a row without edges and a zero bias): not asserted."""
+    for (l, ti), blk in blocks.items():
+        dropped = ~hd.keep(l, ti, ctr)
+        assert dropped.shape == blk.shape, (l, ti)
+        bad = int((blk[dropped] != 0).sum())
+        assert bad == 0, (l, ti, bad, int(dropped.sum()))
+
+
+def act_errors(blocks, want) -> Dict[Tuple[int, int], float]:
+    """Per (l, type index) block |got - want| / |want| (norms over the block, in float64)."""
+    assert sorted(blocks) == sorted(want), (sorted(blocks), sorted(want))
+    return {k: float((blocks[k].double() - want[k].double()).norm() / want[k].double().norm()) for k in blocks}
+
+
+def fp32_act_ratio(make_ref, b: HeteroGraph, p: float, H: int, seeds=(1, 2, 3), ctr: int = 1) -> float:
+    """The yardstick of the activation check: torch's own float32 evaluation of the oracle against its float64
+    evaluation on the host batch ``b``, both under the same host masks — the worst act_errors block over the drop
+    ``seeds``.  make_ref(dtype) builds the oracle in that dtype from one set of parameters."""
+    from unittest import mock
+    n = {t: b.x[t].shape[0] for t in TYPES}
+    r64, r32 = make_ref(torch.float64), make_ref(torch.float32)
+    worst = 0.0
+    for seed in seeds:
+        hd = HostDropout(seed, p, n, H)
+        outs = []
+        with mock.patch.object(torch.nn.functional, "dropout", hd):
+            for ref in (r64, r32):
+                hd.at(ctr)
+                with torch.no_grad():
+                    oracle_forward(ref, b)
+                outs.append(hd.out)
+        worst = max(worst, max(act_errors(outs[1], outs[0]).values()))
+    return worst
+
+
+def glorot_gat_oracle(kw: dict):
+    """OracleHetroGAT for ``kw`` (gat_kwargs) with its projections and attention vectors glorot-initialised and its
+    biases zero, as GATConv.reset_parameters leaves them (the HIP model's lazy projections materialise on a device
+    only); deterministic from torch's seed 1997."""
+    from oracle.pyg_cpu import OracleHetroGAT
+    torch.manual_seed(1997)
+    ref = OracleHetroGAT(feature_widths(kw), kw["node_embedding_size"], kw["heads"], kw["dropout"], kw["concat_path"],
+                         kw["bl_features"], kw["divided_features"], kw["global_feats"], list(kw["mlp_layers"]),
+                         kw["act"], kw["mlp_head_act"], kw["mlp_bn"])
+    for conv in ref.convs[0].convs.values():
+        for w in (conv.att_src, conv.att_dst, conv.lin_src.weight, conv.lin_dst.weight):
+            torch.nn.init.xavier_uniform_(w)
+    return ref
 
 
 def check_eval(pred: torch.Tensor, lv: float, out_ref: torch.Tensor, lv_ref: float, tag=None) -> float:

@@ -189,11 +189,12 @@ def test_fused_step_vs_reference_fixture_global_bn():
 
 
 def test_fused_step_dropout_masks_and_gradients(monkeypatch):
-    """DROPOUT (models.py:358-359, here p = 0.3): the fused step hashes its masks per step — each layer's dropped
-    fraction within 0.05 of p over the batch's rows, and a second replay of the same batch draws new masks (another
-    loss at lr 0).  Given one step's masks — read back from its layer outputs, where a dropped element is an exact
-    zero — the CPU oracle with F.dropout applying those masks gives the same loss (1e-5 relative) and gradients (1e-4
-    of their norm) on the host-collated batch."""
+    """DROPOUT (models.py:358-359, here p = 0.3): the fused step hashes its masks per step from (its seed, its step
+    counter, layer, type, element).  With the masks of the step's counter computed on the host (oracle/dropout_np.py
+    through tests/smallbatch_cases.py's host_dropout: nothing is read back from the step) and applied by the CPU
+    oracle's F.dropout, the oracle gives the same loss (1e-5 relative) and gradients (1e-4 of their norm) on the
+    host-collated batch; a second replay of the same batch draws new masks (another loss at lr 0).  The masks
+    themselves, bit for bit, and the layer outputs: tests/test_gpu_dropmask.py."""
     from hgin.smallbatch import SmallBatchStep
     from oracle.pyg_cpu import OracleHetroGIN, mape
     p = 0.3
@@ -207,34 +208,21 @@ def test_fused_step_dropout_masks_and_gradients(monkeypatch):
                           warmup_ids=[[0, 1]], warmup=1)
     ref = OracleHetroGIN(**kw())
     ref.load_state_dict({k: v.detach().cpu() for k, v in m1.state_dict().items()})
+    torch.cuda.synchronize()
+    seed, ctr = int(step.args.drop_seed), int(step.drop_ctr)
     lv = float(step.step(ids))
     torch.cuda.synchronize()
+    assert int(step.drop_ctr) == ctr + 1
     grads = [_g(q).cpu().clone() for q in m1.parameters()]
     act = step.act.detach().cpu().clone()
     a = step.args
     b = _host_batch(store, ids)
-    types = ("path", "link", "node")
-    n = {t: b.x[t].shape[0] for t in types}
-    assert len(set(n.values())) == 3
-    masks = {}
-    for l in range(a.L):
-        for ti, t in enumerate(types):
-            o = a.act_off[l][ti]
-            masks[(l, t)] = act[o:o + n[t] * a.H].view(n[t], a.H) != 0
-            frac = 1.0 - float(masks[(l, t)].float().mean())
-            assert abs(frac - p) < 0.05, (l, t, frac)
-    calls = {}
-
-    def replay_masks(x, p=0.5, training=True, inplace=False):
-        t = next(t for t in types if n[t] == x.shape[0])
-        l = calls.get(t, 0)
-        calls[t] = l + 1
-        return x * (masks[(l, t)].to(x.dtype) * (1.0 / (1.0 - p)))
-    monkeypatch.setattr(torch.nn.functional, "dropout", replay_masks)
+    n = {t: b.x[t].shape[0] for t in sc.TYPES}
+    hd = sc.host_dropout(monkeypatch, seed, ctr, p, n, a.H)
     out = ref(b.x_dict(), b.edge_index_dict(), b.batch["path"])
     lv_ref = mape(out, b.y.reshape(-1, 1))
     torch.sqrt(lv_ref).backward()
-    assert calls == {t: a.L for t in types}
+    assert hd.calls == {ti: a.L for ti in range(3)}
     assert abs(lv - float(lv_ref)) <= 1e-5 * abs(float(lv_ref)), (lv, float(lv_ref))
     for g, (nm, q) in zip(grads, ref.named_parameters()):
         want = q.grad if q.grad is not None else torch.zeros_like(q)

@@ -139,7 +139,8 @@ def test_fused_gat_step_vs_reference_fixture():
                                      "dropout"])
 def test_fused_gat_step_vs_oracle(variant, monkeypatch):
     """One fused step (Adam at lr 0) against OracleHetroGAT's forward and sqrt-MAPE backward on the host-collated batch;
-    dropout (p 0.3) by replaying the step's own masks (read back from its layer outputs) through the oracle."""
+    dropout (p 0.3) with the masks of the step's counter computed on the host (oracle/dropout_np.py, through
+    tests/smallbatch_cases.py's host_dropout) and applied by the oracle's F.dropout."""
     from hgin.smallbatch import SmallBatchStep
     from oracle.pyg_cpu import mape
     over = {"default": {}, "mlp_bn": dict(mlp_bn=True), "global_feats": dict(global_feats=True, bl_features=True),
@@ -153,31 +154,24 @@ def test_fused_gat_step_vs_oracle(variant, monkeypatch):
     step = SmallBatchStep(m1, torch.optim.Adam(m1.parameters(), lr=0.0), store, batch_size=4, warmup_ids=[[0, 2]],
                           warmup=1)
     torch.cuda.synchronize()
-    # GATConv's bias starts at 0 (reset_parameters): a destination row without edges (path rows past the link count get
-    # no self loop) then outputs exactly 0, which the dropout replay below would read as dropped — nonzero biases keep
-    # every kept element nonzero (written through the parameters, which are views of the step's flat buffer)
-    with torch.no_grad():
-        for conv in m1.convs[0].convs.values():
-            conv.bias.uniform_(-0.1, 0.1)
+    # (GATConv's biases stay at their initial zeros: a destination row without edges outputs exactly 0 whether dropout
+    # keeps it or not, which masks computed on the host do not care about)
     ref = _oracle(m1, kw)   # (after the warm-up step, which advanced MLP_BN's running statistics)
+    if kw["dropout"] > 0:
+        seed, ctr = int(step.args.drop_seed), int(step.drop_ctr)
     lv = float(step.step(ids))
     torch.cuda.synchronize()
     b = _host_batch(store, ids)
     if kw["dropout"] > 0:
-        act = step.act.detach().cpu().clone()
-        a = step.args
-        n = {t: b.x[t].shape[0] for t in ("path", "link", "node")}
-        masks = {}
-        for ti, t in enumerate(("path", "link", "node")):
-            o = a.act_off[0][ti]
-            masks[n[t]] = act[o:o + n[t] * a.H].view(n[t], a.H) != 0
-            assert abs((1.0 - float(masks[n[t]].float().mean())) - kw["dropout"]) < 0.05, t
-        monkeypatch.setattr(torch.nn.functional, "dropout",
-                            lambda x, p=0.5, training=True, inplace=False: x * (masks[x.shape[0]].to(x.dtype) /
-                                                                               (1.0 - p)))
+        import smallbatch_cases as sc
+        assert int(step.drop_ctr) == ctr + 1
+        hd = sc.host_dropout(monkeypatch, seed, ctr, kw["dropout"], {t: b.x[t].shape[0] for t in sc.TYPES},
+                             step.args.H)
     out = ref(b.x_dict(), b.edge_index_dict(), b.batch["path"])
     lv_ref = mape(out, b.y.reshape(-1, 1))
     torch.sqrt(lv_ref).backward()
+    if kw["dropout"] > 0:
+        assert hd.calls == {ti: 1 for ti in range(3)}
     assert abs(lv - float(lv_ref)) <= 1e-5 * abs(float(lv_ref)), (lv, float(lv_ref))
     _check_grads(m1, ref, 1e-6 if kw["mlp_bn"] else 0.0)
     for (n, u), (n2, v) in zip(m1.named_buffers(), ref.named_buffers()):
