@@ -12,28 +12,10 @@
 // Decoder backward: g_z[row] = sum over the row's pairs, in pair order, of g[pair] * z_other[other]
 // (mul then add, no FMA) — a weighted variant of the A3 segmented sum over a CSR of the pairs.
 #include "hgin_common.h"
+#include "hgin_philox.h"   // U4, philox4x32_10 (shared with hgin_linksplit.hip)
 
 namespace hgin {
 namespace {
-
-struct U4 {
-  uint32_t x, y, z, w;
-};
-
-__host__ __device__ __forceinline__ U4 philox4x32_10(U4 ctr, uint32_t k0, uint32_t k1) {
-  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)M0 * ctr.x;
-    const uint64_t p1 = (uint64_t)M1 * ctr.z;
-    const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-    const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-    ctr = U4{hi1 ^ ctr.y ^ k0, lo1, hi0 ^ ctr.w ^ k1, lo0};
-    k0 += W0;
-    k1 += W1;
-  }
-  return ctr;
-}
 
 __device__ __forceinline__ int32_t reduce_range(uint32_t x, uint32_t n) {
   return (int32_t)(((uint64_t)x * (uint64_t)n) >> 32);

@@ -10,6 +10,7 @@ from ._lib import HginError, HginUnavailable, build  # noqa: F401
 from .conv import GINConv, GINLayer, HeteroConv, MessagePassing, reset  # noqa: F401
 from .linkpred import (LINK_OBJECTIVES, LinkPredictor, LinkSegments, hard_negatives, hard_negatives_seg, link_full_metrics, link_full_ranks,  # noqa: F401
                        link_metrics, link_ranks, link_topk, sampled_link_loss)
+from .linksplit import LinkSplit, link_split, link_split_parts, link_split_select  # noqa: F401
 from .models import HetroGAT, HetroGIN  # noqa: F401
 from .qt import QTBaseline  # noqa: F401
 from .train import link_train_step  # noqa: F401
@@ -17,4 +18,4 @@ from .train import link_train_step  # noqa: F401
 __all__ = ["HetroGIN", "HetroGAT", "QTBaseline", "GINLayer", "GINConv", "HeteroConv", "MessagePassing", "reset", "build",
            "HginError", "HginUnavailable", "data", "LinkPredictor", "sampled_link_loss", "link_ranks", "link_metrics",
            "link_full_ranks", "link_full_metrics", "link_topk", "link_train_step", "LINK_OBJECTIVES", "hard_negatives",
-           "LinkSegments", "hard_negatives_seg"]
+           "LinkSegments", "hard_negatives_seg", "LinkSplit", "link_split", "link_split_parts", "link_split_select"]

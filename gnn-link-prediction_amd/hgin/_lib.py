@@ -201,6 +201,10 @@ _SIGS = {
                                      _P, _SZ, ctypes.c_int32, ctypes.c_float, _P, _P, _I64, _I64, _P, _P, _P], _I32),
     "hgin_link_rank_filt_f32": ([_P, _I64, _I64, _U64, _U64, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _P, _P,
                                  _I64, _I64, _P, _P, _P], _I32),
+    "hgin_link_split_parts": ([_P, _I64, _I32, _U64, _U64, _U64, _U64, _P, _P, _P], _I32),
+    "hgin_link_split_select_workspace_size": ([_I64, ctypes.POINTER(_SZ)], _I32),
+    "hgin_link_split_select": ([_P, _P, _I64, _I32, _P, _P, _I64, _P, _SZ, _P], _I32),
+    "hgin_link_split_geometry": ([ctypes.POINTER(_I32), ctypes.POINTER(_I32)], _I32),
     "hgin_aggregate_long_f32": ([_P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I32, _P, _I64, _P,
                                  _SZ, _P], _I32),
     "hgin_aggregate_long_bf16": ([_P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I32, _P, _I64, _P,
@@ -231,7 +235,7 @@ _SIGS = {
     "hgin_trace_enable": ([_I32], _I32),
     "hgin_trace_read": ([ctypes.c_char_p, _SZ], _SZ),
 }
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 def lib() -> ctypes.CDLL:

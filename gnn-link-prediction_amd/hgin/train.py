@@ -36,14 +36,17 @@ def load_optimizer(config: dict, model: torch.nn.Module) -> torch.optim.Optimize
     raise ValueError(f"unknown optimizer {kind!r}")
 
 
-def link_train_step(model, opt, graph, predictor, step: int = 0) -> torch.Tensor:
-    """One link-prediction iteration (no reference counterpart): zero_grad, ``predictor.loss(graph, step=step)``
+def link_train_step(model, opt, graph, predictor, step: int = 0, pos=None, known=None) -> torch.Tensor:
+    """One link-prediction iteration (no reference counterpart): zero_grad, ``predictor.loss(graph, pos, step, known)``
     (``model.encode`` + the fused sampled link loss, fresh negatives per step), backward, ``opt.step()``.
-    ``predictor`` is a ``hgin.linkpred.LinkPredictor`` over ``model``.  Returns the detached device loss."""
+    ``predictor`` is a ``hgin.linkpred.LinkPredictor`` over ``model``.  ``pos`` (default: the relation's own edges in
+    ``graph``) are the positives to score and ``known`` the true edges the drawn negatives avoid, as in
+    ``LinkPredictor.loss``: with a ``hgin.link_split`` pass ``split.train_graph`` and ``pos=split.train_pos``.  Returns
+    the detached device loss."""
     if predictor.model is not model:
         raise ValueError("link_train_step: the predictor was built over another model")
     opt.zero_grad()
-    loss = predictor.loss(graph, step=step)
+    loss = predictor.loss(graph, pos=pos, step=step, known=known)
     loss.backward()
     opt.step()
     return loss.detach()

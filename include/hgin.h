@@ -12,7 +12,8 @@
  *     caller; kernels never allocate.  Scratch comes from a `*_workspace_size` query + caller buffer.
  *   - every call is asynchronous on the caller's HIP stream, passed as `void* stream`
  *     (a `hipStream_t`; NULL = the default stream).  Nothing here synchronises the device, so the calls
- *     can be captured into a hipGraph.
+ *     can be captured into a hipGraph (one exception: hgin_link_split_select, A21, which sizes a
+ *     compaction and says so).
  *   - return value: 0 = ok, > 0 = a hipError_t from the launch, < 0 = argument error (HGIN_E_*).
  *     `hgin_last_error()` returns a thread-local message for the last failing call.
  *   - row-major matrices carry an explicit leading dimension (elements, not bytes).
@@ -28,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HGIN_ABI_VERSION 15
+#define HGIN_ABI_VERSION 16
 
 #define HGIN_OK 0
 #define HGIN_E_ARG (-1)        /* bad size / null pointer / unsupported combination */
@@ -709,6 +710,47 @@ int hgin_link_rank_filt_f32(const int64_t* pos, int64_t n_pos, int64_t k, uint64
                             const float* z_dst, int64_t ld_dst, int64_t F, int32_t* n_greater, int32_t* n_equal,
                             const int32_t* src_seg, const int32_t* dst_ptr, int64_t n_graphs, int64_t n_src,
                             const int32_t* known_rowptr, const int32_t* known_col, void* stream);
+
+/* ---- A21: leakage-free train / valid / test edge splits (NOT IN REFERENCE; build-defined, ABI 16) -----------------
+ * The link head scores edges of a relation that the encoder also passes messages over; an edge that is held out has to
+ * leave the relation and its reverse.  The part of an edge is a function of its endpoint pair, not of its position:
+ *   x = philox4x32_10(counter = {(uint32)s, (uint32)d, 1, 0}, key = {lo32(seed), hi32(seed)})
+ * for an edge (s, d) of the relation in its forward orientation (s = edge_index[0, e], d = edge_index[1, e]).  An edge
+ * (d, s) of the reverse relation evaluates the same rule with swap = 1: s = edge_index[1, e], d = edge_index[0, e].
+ * Word 2 of the counter is 1, so this stream is disjoint from the samplers' (A10 / A13 / A19 / A20: words 2 and 3 are 0).
+ * The bounds are integers computed on the host and passed as uint64 so that 2^32 is representable:
+ *   b_test = floor(test * 2^32), b_val = floor((test + val) * 2^32), b_sup = floor(disjoint * 2^32)
+ *   part 3 (test)                     x.x < b_test
+ *   part 2 (valid)                    not part 3, and x.x < b_val
+ *   part 1 (train, supervision only)  not part 2 or 3, and x.y < b_sup
+ *   part 0 (train, message)           none of the above
+ * Consequences: a pair and its flipped twin get the same part without any join; all copies of a multi-edge get the
+ * same part; the part does not depend on edge order; part sizes are binomial, not exact counts.  Only the low 32 bits
+ * of an endpoint enter the counter (node counts are below 2^31 everywhere else in this header).
+ *   hgin_link_split_parts: one Philox evaluation per edge; part uint8 [E] receives the part code and hist int64 [4]
+ *     is INCREMENTED by the four part counts (the caller zeroes it): per-workgroup LDS counts, then one integer atomic
+ *     per part and workgroup - integer sums do not depend on the order, so the result is deterministic.  E = 0 launches
+ *     nothing.  HGIN_E_ARG for E < 0, a bound above 2^32, b_val < b_test, or a NULL pointer with E > 0.
+ *   hgin_link_split_select: stable stream compaction of the edges whose part's bit is set in keep_mask (bit p = part p,
+ *     4 bits; a part byte is read as part & 3).  out_edge int64 [2, n_out] (row stride n_out) receives the kept columns
+ *     of edge_index (int64 [2, E], row stride E) in input order and out_eid int64 [n_out] their original positions, so
+ *     that edge attributes can follow.  Fixed tiles of tile_edges edges (256 threads x 8); three plain launches:
+ *     (1) per-tile counts, (2) an exclusive scan of the tile counts by one workgroup, scan_width tiles per pass with a
+ *     running carry, (3) scatter with wave-ballot ranks (wave64) and LDS wave offsets.  No workgroup waits on another.
+ *     Between (2) and (3) the scanned total is copied to the host and the stream is synchronised: when it disagrees
+ *     with n_out the call returns HGIN_E_ARG and (3), which would write past the outputs, is not launched.  This is the
+ *     one entry point that synchronises; it cannot be captured into a hipGraph.  E = 0 (then n_out must be 0) launches
+ *     nothing; n_out = 0 with E > 0 runs (1) and (2) only and the outputs may be NULL.
+ *     Workspace: hgin_link_split_select_workspace_size(E) = 4 bytes per tile + 8 bytes per tile + 8, each term rounded
+ *     up to 256.  HGIN_E_ARG for E < 0 or E >= 2^40, keep_mask outside [0, 15], n_out outside [0, E], a NULL pointer
+ *     that would be read or written; HGIN_E_WORKSPACE for a workspace that is NULL or too small.
+ *   hgin_link_split_geometry: tile_edges and scan_width of this build (either pointer may be NULL). */
+int hgin_link_split_parts(const int64_t* edge_index, int64_t E, int swap, uint64_t seed, uint64_t b_test,
+                          uint64_t b_val, uint64_t b_sup, uint8_t* part, int64_t* hist, void* stream);
+int hgin_link_split_select_workspace_size(int64_t E, size_t* bytes);
+int hgin_link_split_select(const int64_t* edge_index, const uint8_t* part, int64_t E, int keep_mask, int64_t* out_edge,
+                           int64_t* out_eid, int64_t n_out, void* ws, size_t ws_bytes, void* stream);
+int hgin_link_split_geometry(int* tile_edges, int* scan_width);
 
 /* ---- F4 widening: HetroGAT's graph attention (models.py:380-506, PyG 2.0.2 GATConv) ---------------------------
  * x_s / x_d: projected source / destination features [N, H * C] (row stride ld*), edges = the relation after
