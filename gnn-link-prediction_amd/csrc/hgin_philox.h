@@ -1,6 +1,7 @@
 // Philox4x32-10 (Salmon et al., SC'11; Random123), the one counter-based generator of libhgin.so: the negative
-// samplers (hgin_linkpred.hip, A10 / A13 / A19 / A20) and the edge-split rule (hgin_linksplit.hip, A21) evaluate this
-// text, pinned by Random123's published known-answer vectors through oracle/hgin_oracle.c.
+// samplers (hgin_linkpred.hip, A10 / A13 / A19 / A20), the edge-split rule (hgin_linksplit.hip, A21) and the neighbour
+// sampler (hgin_neighbor.hip, A22) evaluate this text, pinned by Random123's published known-answer vectors through
+// oracle/hgin_oracle.c.
 #pragma once
 
 #include "hgin_common.h"

@@ -205,6 +205,13 @@ _SIGS = {
     "hgin_link_split_select_workspace_size": ([_I64, ctypes.POINTER(_SZ)], _I32),
     "hgin_link_split_select": ([_P, _P, _I64, _I32, _P, _P, _I64, _P, _SZ, _P], _I32),
     "hgin_link_split_geometry": ([ctypes.POINTER(_I32), ctypes.POINTER(_I32)], _I32),
+    "hgin_neighbor_sample_workspace_size": ([_I64, ctypes.POINTER(_SZ)], _I32),
+    "hgin_neighbor_sample_offsets": ([_P, _I64, _P, _I64, _I32, _P, _P, _SZ, _P], _I32),
+    "hgin_neighbor_sample": ([_P, _P, _P, _I64, _P, _I64, _I32, _U64, ctypes.c_uint32, _I64, _P, _P, _P, _I64, _P],
+                             _I32),
+    "hgin_neighbor_fresh": ([_P, _I64, _P, _I64, _I64, _P, _P], _I32),
+    "hgin_neighbor_map_set": ([_P, _I64, _P, _I64, _I64, _P], _I32),
+    "hgin_neighbor_emit": ([_P, _I64, _P, _P, _I64, _I64, _I64, _P, _P], _I32),
     "hgin_aggregate_long_f32": ([_P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I32, _P, _I64, _P,
                                  _SZ, _P], _I32),
     "hgin_aggregate_long_bf16": ([_P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I32, _P, _I64, _P,

@@ -40,12 +40,18 @@ uniformly from the destinations of its window (all of them, or with ``segments=`
 neighbours of its source: one Philox word mapped onto the r-th non-neighbour, same counters, no rejection loop.  A
 source whose window is all neighbours keeps the unfiltered draw; given negatives (``neg_dst``) are never filtered.
 ``LinkPredictor(filter_negatives=True)`` passes the relation's own edges.  Without ``known`` nothing changes.
+
+Mini-batches (A22, not in the reference): ``link_neighbor_batch`` seeds a ``hgin.neighbor.NeighborSampler`` with a batch's
+positives (and given negatives) and returns them as local rows of the sampled subgraph; ``LinkPredictor.batch_loss``
+draws the negatives ``loss`` would draw, encodes that subgraph only and scores on the fused loss
+(hgin/train.py::link_minibatch_step).
 """
 from __future__ import annotations
 
 import ctypes
 import math
 import weakref
+from typing import NamedTuple, Optional
 
 import torch
 from torch import Tensor
@@ -1050,3 +1056,85 @@ class LinkPredictor:
                 return link_topk(z_src, z_dst, src, k, known, **self._seg_kw(graph))
         finally:
             self.model.train(was_training)
+
+    def batch_loss(self, sampler, pos: Tensor, step: int = 0, known: Tensor = None) -> Tensor:
+        """``loss`` on a neighbour-sampled mini-batch (include/hgin.h A22): the k negatives of every positive of ``pos``
+        (global int64 [2, B]) are drawn as ``loss`` draws them (``negative_edges`` with ``seed``, offset step * B * k,
+        and ``known=`` / ``filter_negatives``: the relation's edges of ``sampler.graph``), ``link_neighbor_batch`` samples
+        the neighbourhood of the sources, destinations and negatives with ``offset=step``, the model encodes that
+        subgraph only, and the fused loss scores the local pairs with the negatives as given ones.  With
+        ``fanouts = [-1] * layers`` this is ``loss(sampler.graph, pos, step, known)`` up to summation order.
+        ``hard`` > 0 and ``graph_local`` are not supported here (ValueError)."""
+        what = "LinkPredictor.batch_loss"
+        if self.hard > 0 or self.graph_local:
+            raise ValueError(f"{what}: hard > 0 and graph_local = True are not supported on sampled mini-batches")
+        from .neighbor import NeighborSampler
+        if not isinstance(sampler, NeighborSampler):
+            raise TypeError(f"{what}: sampler must be a NeighborSampler, got {type(sampler).__name__}")
+        if self.relation[0] not in sampler.num_nodes or self.relation[2] not in sampler.num_nodes:
+            raise ValueError(f"{what}: the sampler's graph lacks a node type of {self.relation!r}")
+        if not isinstance(pos, Tensor) or pos.dtype != torch.long:
+            got = pos.dtype if isinstance(pos, Tensor) else type(pos).__name__
+            raise TypeError(f"{what}: pos must be an int64 edge index [2, B], got {got}")
+        if pos.dim() != 2 or int(pos.size(0)) != 2 or int(pos.size(1)) < 1:
+            raise ValueError(f"{what}: pos must be [2, B] with B >= 1, got {tuple(pos.shape)}")
+        B, n_dst = int(pos.size(1)), sampler.num_nodes[self.relation[2]]
+        if known is None and self.filter_negatives:
+            if self.relation not in sampler.graph.edge_index:
+                raise ValueError(f"{what}: the sampler's graph has no relation {self.relation!r} to filter by")
+            known = sampler.graph.edge_index[self.relation]
+        if known is not None:
+            _known_shape(what, known)
+        ops.require_device(pos, known, what=what)
+        if B * self.k >= 2**31:
+            raise ValueError(f"{what}: need B * k < 2^31 (B = {B}, k = {self.k})")
+        # negative_edges' destinations, with the known CSR keyed by the graph's row count (cached on ``known``)
+        draw_at = int(step) * B * self.k
+        if known is None:
+            neg = sample_negative_dst(B * self.k, n_dst, self.seed, draw_at, pos.device)
+        else:
+            csr = _known_csr(known, sampler.num_nodes[self.relation[0]], n_dst)
+            neg = _sample_filt(pos[0], self.k, self.seed, draw_at, n_dst, None, csr)
+        neg = neg.view(B, self.k)
+        batch = link_neighbor_batch(sampler, self.relation, pos, neg, offset=int(step))
+        g = batch.sub.graph
+        z = self.model.encode(g.x_dict(), g.edge_index_dict())
+        return sampled_link_loss(z[self.relation[0]], z[self.relation[2]], batch.pos, 0, self.seed, 0, self.objective,
+                                 self.temperature, self.alpha, neg_dst=batch.neg_dst)
+
+
+class LinkBatch(NamedTuple):
+    """``link_neighbor_batch``'s result: ``sub`` the ``SampledSubgraph``, ``pos`` the positives as local rows (int64
+    [2, B]), ``neg_dst`` the given negatives as local destination rows (int32 [B, m], range-checked) or None."""
+
+    sub: object
+    pos: Tensor
+    neg_dst: Optional[Tensor]
+
+
+def link_neighbor_batch(sampler, relation, pos: Tensor, neg_dst: Tensor = None, offset: int = 0) -> LinkBatch:
+    """The neighbour-sampled mini-batch of the positives ``pos`` (global int64 [2, B]) of ``relation`` = (src_type,
+    name, dst_type): the seeds are ``pos[0]`` (sources), ``pos[1]`` and, when given, the global integer [B, m]
+    ``neg_dst`` (destinations); ``offset`` is the batch number of ``NeighborSampler.sample``.  Every endpoint is a seed,
+    so its local row is found by a binary search in the sorted seed block, without a host read."""
+    what = "link_neighbor_batch"
+    relation = tuple(relation)
+    if len(relation) != 3:
+        raise ValueError(f"{what}: relation must be (src_type, name, dst_type), got {relation!r}")
+    if not isinstance(pos, Tensor) or pos.dtype != torch.long:
+        got = pos.dtype if isinstance(pos, Tensor) else type(pos).__name__
+        raise TypeError(f"{what}: pos must be an int64 edge index [2, B], got {got}")
+    if pos.dim() != 2 or int(pos.size(0)) != 2:
+        raise ValueError(f"{what}: pos must be [2, B], got {tuple(pos.shape)}")
+    m = _given_shape(what, neg_dst, pos)
+    s_type, d_type = relation[0], relation[2]
+    dst = pos[1] if m == 0 else torch.cat([pos[1], neg_dst.reshape(-1).long()])
+    seeds = {s_type: torch.cat([pos[0], dst])} if s_type == d_type else {s_type: pos[0], d_type: dst}
+    sub = sampler.sample(seeds, offset=offset)
+    local = torch.stack([sub._rows(s_type, pos[0]), sub._rows(d_type, pos[1])])
+    neg_local = None
+    if m:
+        neg_local = sub._rows(d_type, neg_dst.long().contiguous()).to(torch.int32)
+        _mark_checked(neg_local, int(sub.n_id[d_type].numel()))
+    return LinkBatch(sub, local, neg_local)
+

@@ -52,6 +52,22 @@ def link_train_step(model, opt, graph, predictor, step: int = 0, pos=None, known
     return loss.detach()
 
 
+def link_minibatch_step(model, opt, sampler, predictor, pos, step: int = 0, known=None) -> torch.Tensor:
+    """One link-prediction iteration on a neighbour-sampled mini-batch (no reference counterpart): zero_grad,
+    ``predictor.batch_loss(sampler, pos, step, known)`` (k fresh negatives per positive, the sampled neighbourhood of the
+    batch's endpoints from ``sampler`` = a ``hgin.NeighborSampler``, ``model.encode`` of that subgraph only, the fused
+    link loss), backward, ``opt.step()``.  ``pos`` are this batch's positives (global int64 [2, B]).  Messages flow over
+    whatever is in the sampler's graph, so the positives should come from ``hgin.link_split``'s ``disjoint`` part.
+    Returns the detached device loss."""
+    if predictor.model is not model:
+        raise ValueError("link_minibatch_step: the predictor was built over another model")
+    opt.zero_grad()
+    loss = predictor.batch_loss(sampler, pos, step=step, known=known)
+    loss.backward()
+    opt.step()
+    return loss.detach()
+
+
 def train_step(model, opt, graph, loss_func=mape, reducer: Optional[GradAllReducer] = None,
                sync_metric: bool = False, fused_loss: bool = True):
     """One train.py:31-44 iteration.  ``fused_loss`` (default): when the loss is train.py's ``mape`` and the

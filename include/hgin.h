@@ -752,6 +752,69 @@ int hgin_link_split_select(const int64_t* edge_index, const uint8_t* part, int64
                            int64_t* out_eid, int64_t n_out, void* ws, size_t ws_bytes, void* stream);
 int hgin_link_split_geometry(int* tile_edges, int* scan_width);
 
+/* ---- A22: neighbour-sampled mini-batches (NOT IN REFERENCE; build-defined; added to ABI 16 without a bump) ---------
+ * The link head trains on batches of positive edges; the encoder then needs only a sampled L-hop neighbourhood of their
+ * endpoints.  The section is purely additive (no earlier entry point changes), so HGIN_ABI_VERSION stays 16.
+ *
+ * The sampling rule, for one hop of one relation r = (s_type, name, d_type) that has slot r_slot in the sampler's
+ * relation list: the relation's CSR by destination (hgin_csr_build, key_row = 1: rowptr, col, perm), a frontier of global
+ * destination ids v_0 .. v_{n-1}, a fanout f (1 <= f <= 128, or -1 = every neighbour), seed (uint64) and offset (uint32,
+ * the batch number).  Picks of frontier node v, d = rowptr[v + 1] - rowptr[v]:
+ *   f == -1 or d <= f: every CSR position 0 .. d - 1; no Philox word is consumed.
+ *   otherwise Floyd's subset algorithm (an exactly uniform f-subset of [0, d), no rejection loop): for i = 0 .. f - 1
+ *     J = d - f + i
+ *     w_i = word i & 3 of philox4x32_10(counter = {(uint32)v, offset, 2, (uint32)(r_slot * 64 + (i >> 2))},
+ *                                      key = {lo32(seed), hi32(seed)})
+ *     t = hi32((uint64)w_i * (J + 1));  pick t if it has not been picked yet, else pick J.
+ *   Word 2 of the counter is 2, so this stream is disjoint from the negative samplers' (A10 / A13 / A19 / A20: word 2 is
+ *   0) and from the split rule's (A21: word 2 is 1).
+ *   The picked positions are emitted in ascending CSR position; pick p gives source col[rowptr[v] + p] and original edge
+ *   position perm[rowptr[v] + p].
+ * A node's picks depend only on (seed, offset, r_slot, v): not on where v sits in the frontier, not on the batch.
+ *
+ * The subgraph rule, for seeds = {type: ids} (repeats allowed, a type may be absent) and fanouts f_1 .. f_L:
+ *   Local rows of a type: the unique seeds, ascending; then for hop h = 1 .. L in order the nodes of that type first
+ *     reached at hop h, ascending by global id.
+ *   Hop h: for each relation in list order, every node of d_type that joined at hop h - 1 (hop 1: the seeds) is
+ *     expanded once with fanout f_h.  A node is expanded at most once per relation in a batch, at the hop where it first
+ *     appears; nodes first reached at hop L are not expanded.
+ *   Edges of relation r: hop-major, then frontier (local-row) order, then ascending CSR position, as (local src, local
+ *     dst) int64 [2, E_r]; e_id[r] holds the original edge positions in the same order.  Every in-edge of an expanded
+ *     node is contiguous and keeps its original relative order, so the stable CSR of the subgraph sums a fully sampled
+ *     row in the full graph's order.
+ *   The output does not depend on execution order: new nodes are found with a resident dense global -> local map per
+ *   type (int32, -1 = not in the batch) that is only read while a hop's candidates are tested, a sort + unique of the
+ *   candidates, and a write of the new rows before the hop's edges are relabelled.
+ *
+ * Entry points (plain launches; no workgroup waits on another; nothing synchronises):
+ *   hgin_neighbor_sample_offsets: off int64 [n_frontier + 1] = the exclusive scan of min(d, f) (d when f = -1) over the
+ *     frontier, off[n_frontier] = the number of sampled edges, which the caller reads to size the outputs.  Three
+ *     launches: per-tile counts + scan (256 nodes), a scan of the tile sums by one workgroup, the tile offsets added.
+ *     A frontier id outside [0, n_rows) counts as an empty row.  Workspace: hgin_neighbor_sample_workspace_size
+ *     (n_frontier) = 8 bytes per tile + 8, rounded up to 256.
+ *   hgin_neighbor_sample: out_src / out_eid int64 [n_out] at off[i] .. off[i + 1] for frontier node i; a lane group per
+ *     node (8, 16 or 64 lanes by f), at most two picks per lane in registers, the membership test of a Floyd step one
+ *     ballot, the ascending order a rank count: O(f^2) per node whatever d is.  A store is also guarded by n_out.
+ *   hgin_neighbor_fresh: out[j] = src[j] when map[src[j]] < 0 (not yet a row of the batch), else sentinel.
+ *   hgin_neighbor_map_set: map[ids[i]] = base + i for base >= 0; -1 for base < 0 (the clean-up).  ids are distinct.
+ *   hgin_neighbor_emit: out_edge int64 [2, n_edges] (row stride n_edges): row 0 = map_src[src[j]], row 1 = dst_base + i
+ *     for the frontier slot i with off[i] <= j < off[i + 1] (a binary search per edge).
+ * Status: HGIN_E_ARG before any launch for a NULL pointer that would be read or written, f outside {-1} u [1, 128],
+ *   n_rows / n_nodes / n_frontier outside [0, 2^31), r_slot outside [0, 2^26), n_out above n_frontier * f, edges of an
+ *   empty frontier; HGIN_E_WORKSPACE for a workspace that is NULL or too small.  Empty inputs launch nothing. */
+int hgin_neighbor_sample_workspace_size(int64_t n_frontier, size_t* bytes);
+int hgin_neighbor_sample_offsets(const int32_t* rowptr, int64_t n_rows, const int64_t* frontier, int64_t n_frontier,
+                                 int f, int64_t* off, void* ws, size_t ws_bytes, void* stream);
+int hgin_neighbor_sample(const int32_t* rowptr, const int32_t* col, const int32_t* perm, int64_t n_rows,
+                         const int64_t* frontier, int64_t n_frontier, int f, uint64_t seed, uint32_t offset,
+                         int64_t r_slot, const int64_t* off, int64_t* out_src, int64_t* out_eid, int64_t n_out,
+                         void* stream);
+int hgin_neighbor_fresh(const int32_t* map, int64_t n_nodes, const int64_t* src, int64_t n, int64_t sentinel,
+                        int64_t* out, void* stream);
+int hgin_neighbor_map_set(int32_t* map, int64_t n_nodes, const int64_t* ids, int64_t n, int64_t base, void* stream);
+int hgin_neighbor_emit(const int32_t* map_src, int64_t n_src_nodes, const int64_t* src, const int64_t* off,
+                       int64_t n_frontier, int64_t dst_base, int64_t n_edges, int64_t* out_edge, void* stream);
+
 /* ---- F4 widening: HetroGAT's graph attention (models.py:380-506, PyG 2.0.2 GATConv) ---------------------------
  * x_s / x_d: projected source / destination features [N, H * C] (row stride ld*), edges = the relation after
  * GATConv's self-loop handling, as CSR by destination (rowptr, col) and CSC by source (cptr, cdst, cpos = the CSR
