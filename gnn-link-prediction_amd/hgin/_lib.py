@@ -212,6 +212,13 @@ _SIGS = {
     "hgin_neighbor_fresh": ([_P, _I64, _P, _I64, _I64, _P, _P], _I32),
     "hgin_neighbor_map_set": ([_P, _I64, _P, _I64, _I64, _P], _I32),
     "hgin_neighbor_emit": ([_P, _I64, _P, _P, _I64, _I64, _I64, _P, _P], _I32),
+    "hgin_link_lse_workspace_size": ([_I64, _I64, _I64, ctypes.POINTER(_SZ)], _I32),
+    "hgin_link_lse_fwd_f32": ([_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _I64, ctypes.c_float, _P, _P, _P, _P, _SZ, _P],
+                              _I32),
+    "hgin_link_lse_bwd_src_f32": ([_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _I64, ctypes.c_float, _P, _P, _P, _P, _P,
+                                   _I64, _P, _SZ, _P], _I32),
+    "hgin_link_lse_bwd_dst_f32": ([_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _I64, ctypes.c_float, _P, _P, _P, _P, _P,
+                                   _I64, _P, _SZ, _P], _I32),
     "hgin_aggregate_long_f32": ([_P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I32, _P, _I64, _P,
                                  _SZ, _P], _I32),
     "hgin_aggregate_long_bf16": ([_P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I32, _P, _I64, _P,

@@ -45,6 +45,12 @@ Mini-batches (A22, not in the reference): ``link_neighbor_batch`` seeds a ``hgin
 positives (and given negatives) and returns them as local rows of the sampled subgraph; ``LinkPredictor.batch_loss``
 draws the negatives ``loss`` would draw, encodes that subgraph only and scores on the fused loss
 (hgin/train.py::link_minibatch_step).
+
+Full softmax (A23, not in the reference): ``link_lse`` is the log-sum-exp of a source's scores over *every* destination
+(known edges masked), forward and backward on the matrix cores without a score matrix (csrc/hgin_linklse.hip);
+``full_softmax_link_loss`` is the per-positive cross-entropy over it, ``LinkPredictor.full_loss`` /
+``batch_full_loss`` train on it (the latter with a mini-batch's destination seeds as in-batch negatives);
+``link_lse_unfused`` is the kept torch baseline.
 """
 from __future__ import annotations
 
@@ -896,6 +902,209 @@ def _hard_negatives(what, z_src, z_dst, pos, m, known, seed, offset, segments):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------
+# A23: full-candidate softmax loss (NOT IN REFERENCE)
+# ---------------------------------------------------------------------------------------------------
+def _distinct_sources(what: str, src: Tensor, n_src: int) -> None:
+    """``src`` holds distinct values in [0, n_src): IndexError / ValueError otherwise.  One host sync, once per tensor
+    version (cached on the tensor, as ``_given_negatives`` does it)."""
+    key = int(n_src)
+    cache = getattr(src, "_hgin_distinct", None)
+    ver = src._version
+    if cache is not None and cache[0] == ver and key in cache[1]:
+        return
+    srt = torch.sort(src).values
+    dup = (srt[1:] == srt[:-1]).any().to(torch.long)
+    lo, hi, dup = torch.stack([srt[0], srt[-1], dup]).tolist()
+    if lo < 0 or hi >= n_src:
+        raise IndexError(f"{what}: src index out of range [0, {n_src})")
+    if dup:
+        raise ValueError(f"{what}: src must hold distinct sources (a repeated value was found)")
+    if cache is None or cache[0] != ver:
+        cache = (ver, set())
+    cache[1].add(key)
+    try:
+        src._hgin_distinct = cache
+    except (AttributeError, RuntimeError):
+        pass
+
+
+def _lse_operands(what: str, z_src: Tensor, z_dst: Tensor, src: Tensor, temperature, known):
+    """Checked operands of ``link_lse`` / ``link_lse_unfused``: (z_src, z_dst, src, inv_t, rowptr, col)."""
+    for name, z in (("z_src", z_src), ("z_dst", z_dst)):
+        if z.dtype != torch.float32:
+            raise TypeError(f"{what}: {name} must be float32 (the fused link kernels are fp32 only), got {z.dtype}")
+        if z.dim() != 2:
+            raise RuntimeError(f"{what}: {name} must be [N, F]")
+    if z_src.size(1) != z_dst.size(1):
+        raise RuntimeError(f"{what}: embedding widths differ")
+    if not isinstance(src, Tensor) or src.dtype != torch.long or src.dim() != 1:
+        got = f"{src.dtype} {tuple(src.shape)}" if isinstance(src, Tensor) else type(src).__name__
+        raise ValueError(f"{what}: src must be an int64 [Q] tensor, got {got}")
+    temperature = float(temperature)
+    if not (math.isfinite(temperature) and temperature > 0.0):
+        raise ValueError(f"{what}: temperature must be finite and > 0, got {temperature}")
+    if known is not None:
+        _known_shape(what, known)
+    Q = int(src.numel())
+    n_src, n_dst, F = int(z_src.size(0)), int(z_dst.size(0)), int(z_src.size(1))
+    if Q < 1 or Q >= 2**31:
+        raise ValueError(f"{what}: need 1 <= Q < 2^31 (Q = {Q})")
+    if F < 1 or n_src < 1 or n_dst < 1:
+        raise ValueError(f"{what}: embeddings need at least one row and one feature")
+    src = src.contiguous()
+    _distinct_sources(what, src, n_src)      # plain torch: a repeated source is reported wherever the tensor lives
+    ops.require_device(z_src, z_dst, src, known, what=what)
+    rowptr = col = None
+    if known is not None:
+        rowptr, col = _known_csr(known, n_src, n_dst)
+    inv_t = ctypes.c_float(1.0 / temperature).value    # fl32(1 / temperature), the value the kernels multiply by
+    return ops._rowmajor(z_src), ops._rowmajor(z_dst), src, inv_t, rowptr, col
+
+
+class _LinkLseFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z_src, z_dst, src, inv_t: float, rowptr, col):
+        dev = z_src.device
+        Q, n_src, n_dst, F = int(src.numel()), int(z_src.size(0)), int(z_dst.size(0)), int(z_src.size(1))
+        nbytes = ctypes.c_size_t(0)
+        _lib.check(_lib.lib().hgin_link_lse_workspace_size(Q, n_dst, F, ctypes.byref(nbytes)),
+                   "hgin_link_lse_workspace_size")
+        ws = ops._workspace(nbytes.value, dev)
+        lse = torch.empty(Q, dtype=torch.float32, device=dev)
+        _lib.call("hgin_link_lse_fwd_f32", ops._p(src), Q, n_src, n_dst, ops._p(z_src), z_src.stride(0), ops._p(z_dst),
+                  z_dst.stride(0), F, inv_t, ops._p(rowptr), ops._p(col), ops._p(lse), ops._p(ws), nbytes.value,
+                  ops._stream(lse))
+        ctx.inv_t, ctx.ws_bytes, ctx.known = inv_t, nbytes.value, (rowptr, col)
+        ctx.save_for_backward(z_src, z_dst, src, lse)
+        return lse
+
+    @staticmethod
+    def backward(ctx, g):
+        z_src, z_dst, src, lse = ctx.saved_tensors
+        rowptr, col = ctx.known
+        g = g.to(torch.float32).contiguous()
+        Q, n_src, n_dst, F = int(src.numel()), int(z_src.size(0)), int(z_dst.size(0)), int(z_src.size(1))
+        g_src = g_dst = None
+        ws = None       # one workspace for both kernels: they run one after the other on this stream
+        for i, name in ((0, "hgin_link_lse_bwd_src_f32"), (1, "hgin_link_lse_bwd_dst_f32")):
+            if not ctx.needs_input_grad[i]:
+                continue
+            out = torch.empty_like(z_src if i == 0 else z_dst, memory_format=torch.contiguous_format)
+            if ws is None:
+                ws = ops._workspace(ctx.ws_bytes, z_src.device)
+            _lib.call(name, ops._p(src), Q, n_src, n_dst, ops._p(z_src), z_src.stride(0), ops._p(z_dst),
+                      z_dst.stride(0), F, ctx.inv_t, ops._p(rowptr), ops._p(col), ops._p(lse), ops._p(g), ops._p(out),
+                      out.stride(0), ops._p(ws), ctx.ws_bytes, ops._stream(out))
+            if i == 0:
+                g_src = out
+            else:
+                g_dst = out
+        return g_src, g_dst, None, None, None, None
+
+
+def link_lse(z_src: Tensor, z_dst: Tensor, src: Tensor, temperature: float = 1.0, known: Tensor = None) -> Tensor:
+    """float32 [Q] (include/hgin.h A23): for every source ``src[q]`` (int64 [Q], distinct: checked once per tensor
+    version with one host sync, ValueError) the log-sum-exp over *every* destination c of
+    <z_src[src[q]], z_dst[c]> / temperature, minus the c with (src[q], c) in ``known`` (an edge index [2, M]; None: every
+    destination); -inf for a source whose destinations are all known.  The scores are the bits ``link_full_ranks`` /
+    ``link_topk`` compare; no [Q, n_dst] matrix exists in the forward or in the backward (two kernels that recompute the
+    scores, csrc/hgin_linklse.hip); forward and gradients are run-to-run identical."""
+    what = "link_lse"
+    z_src, z_dst, src, inv_t, rowptr, col = _lse_operands(what, z_src, z_dst, src, temperature, known)
+    return _LinkLseFn.apply(z_src, z_dst, src, inv_t, rowptr, col)
+
+
+LSE_UNFUSED_BYTES = 1 << 30     # fp32 scores per chunk of the unfused baseline
+
+
+def link_lse_unfused(z_src: Tensor, z_dst: Tensor, src: Tensor, temperature: float = 1.0, known: Tensor = None,
+                     chunk_rows: int = None) -> Tensor:
+    """``link_lse`` as plain torch, the kept baseline the fused path is checked and timed against: chunks of query rows
+    (about 1 GB of fp32 scores each, or ``chunk_rows``) of ``z_src[src] @ z_dst.T * fl32(1 / temperature)``, known edges
+    set to -inf, ``torch.logsumexp``.  It materialises a chunk of the [Q, n_dst] matrix, and autograd keeps it."""
+    what = "link_lse_unfused"
+    z_src, z_dst, src, inv_t, rowptr, col = _lse_operands(what, z_src, z_dst, src, temperature, known)
+    Q, n_dst = int(src.numel()), int(z_dst.size(0))
+    rows = int(chunk_rows) if chunk_rows else max(1, LSE_UNFUSED_BYTES // (4 * n_dst))
+    out = []
+    for a in range(0, Q, rows):
+        s = src[a:a + rows]
+        t = (z_src[s] @ z_dst.t()) * inv_t
+        if rowptr is not None:
+            beg, end = rowptr[s].long(), rowptr[s + 1].long()
+            deg = end - beg
+            qi = torch.repeat_interleave(torch.arange(s.numel(), device=s.device), deg)
+            first = torch.repeat_interleave(beg - (torch.cumsum(deg, 0) - deg), deg)
+            ci = col[(torch.arange(qi.numel(), device=s.device) + first)].long() if qi.numel() else qi
+            mask = torch.zeros_like(t, dtype=torch.bool)
+            mask[qi, ci] = True
+            t = t.masked_fill(mask, float("-inf"))
+        out.append(torch.logsumexp(t, 1))
+    return torch.cat(out)
+
+
+def _full_softmax_plan(pos: Tensor, known: Optional[Tensor], n_src: int, n_dst: int):
+    """(u, cnt, known u pos or None) of the positives, cached on ``pos`` per (its version, ``known`` and its version): u
+    the distinct sources in ascending order, cnt how many positives each has."""
+    cache = getattr(pos, "_hgin_full_softmax", None)
+    ver = pos._version
+    if cache is not None and cache[0] == ver and cache[1] == (n_src, n_dst) and \
+            (cache[2] is None) == (known is None) and \
+            (known is None or (cache[2]() is known and cache[3] == known._version)):
+        return cache[4]
+    u, cnt = torch.unique(pos[0], return_counts=True)
+    try:
+        u._hgin_distinct = (u._version, {int(n_src)})   # distinct by construction, in range by relation_graph's check
+    except (AttributeError, RuntimeError):
+        pass
+    both = None if known is None else torch.cat([known, pos], 1)
+    plan = (u, cnt.to(torch.float32), both)
+    try:
+        pos._hgin_full_softmax = (ver, (n_src, n_dst), None if known is None else weakref.ref(known),
+                                  None if known is None else known._version, plan)
+    except (AttributeError, RuntimeError):
+        pass
+    return plan
+
+
+def full_softmax_link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, temperature: float = 1.0,
+                           known: Tensor = None) -> Tensor:
+    """Softmax cross-entropy of every positive (s, d) of ``pos`` (int64 [2, E]) against *every* destination (a scalar):
+    mean over the positives of log sum_c exp(score(s, c) / T) - score(s, d) / T, on ``link_lse`` (one query per distinct
+    source) and ``dot_decode``.  ``known`` = None: the sum runs over every destination,
+    loss = (sum_q cnt_q lse_q - sum_e s_e) / E.  With ``known`` (an edge index [2, M]) a source's other true edges leave
+    the denominator while the positive stays in its own: lse_neg = ``link_lse`` filtered by ``known`` and ``pos``
+    together, loss = mean_e softplus(lse_neg[s_e] - s_e).  Deterministic forward and backward: the per-positive read of
+    lse_neg is a ``dot_decode`` of a one-column embedding against a column of ones, whose backward is the store-and-sum
+    over the static CSC of ``pos``."""
+    what = "full_softmax_link_loss"
+    for name, z in (("z_src", z_src), ("z_dst", z_dst)):
+        if z.dtype != torch.float32:
+            raise TypeError(f"{what}: {name} must be float32 (the fused link kernels are fp32 only), got {z.dtype}")
+    temperature = float(temperature)
+    if not (math.isfinite(temperature) and temperature > 0.0):
+        raise ValueError(f"{what}: temperature must be finite and > 0, got {temperature}")
+    if known is not None:
+        _known_shape(what, known)
+    ops.require_device(z_src, z_dst, pos, known, what=what)
+    ops.check_edge_index(pos)
+    E = int(pos.size(1))
+    if E < 1:
+        raise ValueError(f"{what}: need E >= 1")
+    n_src, n_dst = int(z_src.size(0)), int(z_dst.size(0))
+    s_e = dot_decode(z_src, z_dst, pos) * ctypes.c_float(1.0 / temperature).value   # range-checks pos (relation_graph)
+    u, cnt, both = _full_softmax_plan(pos, known, n_src, n_dst)
+    if known is None:
+        lse = link_lse(z_src, z_dst, u, temperature)
+        return ((cnt * lse).sum() - s_e.sum()) / E
+    lse_neg = link_lse(z_src, z_dst, u, temperature, known=both)
+    col = torch.zeros(n_src, dtype=torch.float32, device=z_src.device).index_copy(0, u, lse_neg)
+    ones = torch.ones(n_dst, 1, dtype=torch.float32, device=z_src.device)
+    lse_e = dot_decode(col.unsqueeze(1), ones, pos)     # lse_neg of every positive's source: x * 1.0 is exact
+    return torch.nn.functional.softplus(lse_e - s_e).mean()
+
+
 class LinkPredictor:
     """Link-prediction head over a model's node embeddings: ``relation`` = (src_type, name, dst_type), k uniform
     negatives per positive, dot-product decoder, and the training objective of ``sampled_link_loss`` ("bce" by
@@ -1101,6 +1310,58 @@ class LinkPredictor:
         z = self.model.encode(g.x_dict(), g.edge_index_dict())
         return sampled_link_loss(z[self.relation[0]], z[self.relation[2]], batch.pos, 0, self.seed, 0, self.objective,
                                  self.temperature, self.alpha, neg_dst=batch.neg_dst)
+
+    def _no_full(self, what: str) -> None:
+        if self.hard > 0 or self.graph_local:
+            raise ValueError(f"{what}: hard > 0 and graph_local = True are not supported by the full softmax loss")
+
+    def full_loss(self, graph, pos: Tensor = None, known: Tensor = None) -> Tensor:
+        """``full_softmax_link_loss`` of ``pos`` (default: the relation's own edges) at the predictor's ``temperature``:
+        every positive against every destination of the graph (include/hgin.h A23); k, seed and the objective play no
+        part.  ``known`` (an edge index; default with ``filter_negatives``: the relation's own edges) takes a source's
+        other true edges out of the denominator.  ``hard`` > 0 and ``graph_local`` are not supported (ValueError)."""
+        self._no_full("LinkPredictor.full_loss")
+        pos = self._pos(graph, pos)
+        z = self.model.encode(graph.x_dict(), graph.edge_index_dict())
+        return full_softmax_link_loss(z[self.relation[0]], z[self.relation[2]], pos, self.temperature,
+                                      **self._known_kw(graph, known))
+
+    def batch_full_loss(self, sampler, pos: Tensor, step: int = 0, known: Tensor = None) -> Tensor:
+        """The softmax loss with in-batch negatives on a neighbour-sampled mini-batch: ``link_neighbor_batch`` seeds the
+        sampler with the positives ``pos`` (global int64 [2, B]) alone (``offset=step``), the model encodes that subgraph,
+        and every positive is scored against the destination-type seeds of the batch (the leading rows of the local
+        embedding: a slice, no gather) with ``full_softmax_link_loss``.  The batch's own positives are always known
+        edges (a source's other positives leave its denominator); with ``known=`` or ``filter_negatives`` (the relation's
+        edges of ``sampler.graph``) so are the known edges whose endpoints are both seeds
+        (``SampledSubgraph.local_edges``).  ``hard`` > 0 and ``graph_local`` are not supported (ValueError)."""
+        what = "LinkPredictor.batch_full_loss"
+        self._no_full(what)
+        from .neighbor import NeighborSampler
+        if not isinstance(sampler, NeighborSampler):
+            raise TypeError(f"{what}: sampler must be a NeighborSampler, got {type(sampler).__name__}")
+        if self.relation[0] not in sampler.num_nodes or self.relation[2] not in sampler.num_nodes:
+            raise ValueError(f"{what}: the sampler's graph lacks a node type of {self.relation!r}")
+        if not isinstance(pos, Tensor) or pos.dtype != torch.long:
+            got = pos.dtype if isinstance(pos, Tensor) else type(pos).__name__
+            raise TypeError(f"{what}: pos must be an int64 edge index [2, B], got {got}")
+        if pos.dim() != 2 or int(pos.size(0)) != 2 or int(pos.size(1)) < 1:
+            raise ValueError(f"{what}: pos must be [2, B] with B >= 1, got {tuple(pos.shape)}")
+        if known is None and self.filter_negatives:
+            if self.relation not in sampler.graph.edge_index:
+                raise ValueError(f"{what}: the sampler's graph has no relation {self.relation!r} to filter by")
+            known = sampler.graph.edge_index[self.relation]
+        if known is not None:
+            _known_shape(what, known)
+        ops.require_device(pos, known, what=what)
+        s_type, d_type = self.relation[0], self.relation[2]
+        batch = link_neighbor_batch(sampler, self.relation, pos, None, offset=int(step))
+        g = batch.sub.graph
+        z = self.model.encode(g.x_dict(), g.edge_index_dict())
+        local_known = batch.pos
+        if known is not None:
+            local_known = torch.cat([batch.pos, batch.sub.local_edges(s_type, d_type, known)], 1)
+        return full_softmax_link_loss(z[s_type], z[d_type][:batch.sub.n_seed[d_type]], batch.pos, self.temperature,
+                                      known=local_known)
 
 
 class LinkBatch(NamedTuple):

@@ -84,6 +84,27 @@ class SampledSubgraph:
             raise IndexError(f"SampledSubgraph.local: an id is not a {node_type!r} seed of this batch")
         return rows
 
+    def local_edges(self, src_type: str, dst_type: str, edge_index: Tensor) -> Tensor:
+        """The edges of the global int64 ``edge_index`` [2, M] (sources of ``src_type``, destinations of ``dst_type``)
+        whose endpoints are both seeds of the batch, relabelled to local rows (int64 [2, M']; order kept): a binary
+        search into the two sorted seed blocks plus an equality test, in torch; no value is read on the host."""
+        for t in (src_type, dst_type):
+            if t not in self.n_id:
+                raise ValueError(f"SampledSubgraph.local_edges: unknown node type {t!r}")
+        if not isinstance(edge_index, Tensor) or edge_index.dtype != torch.int64:
+            got = edge_index.dtype if isinstance(edge_index, Tensor) else type(edge_index).__name__
+            raise TypeError(f"SampledSubgraph.local_edges: edge_index must be an int64 tensor, got {got}")
+        if edge_index.dim() != 2 or int(edge_index.size(0)) != 2:
+            raise ValueError(f"SampledSubgraph.local_edges: edge_index must be [2, M], got {tuple(edge_index.shape)}")
+        ns, nd = self.n_seed[src_type], self.n_seed[dst_type]
+        if ns == 0 or nd == 0 or edge_index.size(1) == 0:
+            return edge_index.new_empty((2, 0))
+        s_seeds, d_seeds = self.n_id[src_type][:ns], self.n_id[dst_type][:nd]
+        rs = torch.searchsorted(s_seeds, edge_index[0].contiguous()).clamp_(max=ns - 1)
+        rd = torch.searchsorted(d_seeds, edge_index[1].contiguous()).clamp_(max=nd - 1)
+        keep = (s_seeds[rs] == edge_index[0]) & (d_seeds[rd] == edge_index[1])
+        return torch.stack([rs[keep], rd[keep]])
+
 
 class NeighborSampler:
     """Samples the L-hop neighbourhood of a batch of seed nodes out of ``graph`` (include/hgin.h A22).

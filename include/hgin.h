@@ -815,6 +815,48 @@ int hgin_neighbor_map_set(int32_t* map, int64_t n_nodes, const int64_t* ids, int
 int hgin_neighbor_emit(const int32_t* map_src, int64_t n_src_nodes, const int64_t* src, const int64_t* off,
                        int64_t n_frontier, int64_t dst_base, int64_t n_edges, int64_t* out_edge, void* stream);
 
+/* ---- A23: full-candidate softmax link loss (NOT IN REFERENCE; build-defined; added to ABI 16 without a bump) -------
+ * For query q (s = src[q]; src int64 [n_query], DISTINCT rows of z_src, the caller guarantees 0 <= s < n_src),
+ * inv_t = fl32(1 / temperature) and the known CSR by source of A15 / A16 / A20 (known_rowptr int32 [n_src + 1] /
+ * known_col int32, columns sorted within a row, no duplicates; known_rowptr = NULL: no known edges):
+ *   cand(q) = { c in [0, n_dst) : (s, c) not in known }
+ *   t[q, c] = fl32(score(q, c) * inv_t)      score = the A15 / A16 bits (exact-fp32 matrix-core dot products, features
+ *                                            in blocks of 8 ascending, inside a block the pairs (0, 4) .. (3, 7))
+ *   lse[q]  = log sum_{c in cand(q)} exp(t[q, c])      float [n_query]; -inf when cand(q) is empty
+ * computed with a running maximum (no overflow for any finite t).  Backward for an upstream g float [n_query] and
+ * P[q, c] = exp(t[q, c] - lse[q]) for c in cand(q), else 0:
+ *   g_src[src[q], :] = g[q] * inv_t * sum_c P[q, c] * z_dst[c, :]         (rows of z_src not in src: zero)
+ *   g_dst[c, :]      =        inv_t * sum_q g[q] * P[q, c] * z_src[src[q], :]
+ * Where lse[q] = -inf, P is 0 and both gradients are 0 (no NaN, no inf).  With repeated sources g_src keeps one of the
+ * repeats' rows: callers pass distinct sources.
+ * No [n_query, n_dst] object exists in any pass: the forward is the A15 sweep (128 queries x 128-destination tiles)
+ * with an online log-sum-exp epilogue, known neighbours masked inside the sweep (they are the dominant terms of a
+ * trained model: subtracting them afterwards would keep no digits); both backward kernels recompute t from the operands
+ * and lse, and use the 128 x 128 tile of g * inv_t * P as the operand of a second matrix-core product (g_src: a
+ * workgroup owns 128 queries x 128 output features (256 once F > 128) and sweeps the destinations; g_dst: it owns 128
+ * destinations and sweeps the queries; F > 256: one workgroup per chunk of 256 output features).  Where the stationary side is too short
+ * to fill the machine the swept side is split (the A15 plan; for g_dst with the roles swapped) and the splits' partials
+ * are added in ascending order.  No float atomics: forward and gradients are run-to-run identical.  The only inexact
+ * steps are exp, log and the order of the sums.
+ * Workspace: hgin_link_lse_workspace_size covers all three calls (forward: 8 bytes per (split, query); a gradient with
+ * more than one split: 4 F bytes per (split, output row)).  fp32 only; rows need no alignment (16-byte loads are used
+ * when F, both strides and both bases allow them).  1 <= n_query < 2^31, 1 <= n_src, n_dst < 2^31, 1 <= F < 2^24,
+ * ld >= F, inv_t finite and > 0, split partials of a gradient (splits x output rows x F) below 2^39 floats: HGIN_E_ARG
+ * before any launch otherwise, also for a NULL pointer and for known_rowptr without known_col; HGIN_E_WORKSPACE for a workspace that is needed and NULL or too small. */
+int hgin_link_lse_workspace_size(int64_t n_query, int64_t n_dst, int64_t F, size_t* bytes);
+int hgin_link_lse_fwd_f32(const int64_t* src, int64_t n_query, int64_t n_src, int64_t n_dst, const float* z_src,
+                          int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F, float inv_t,
+                          const int32_t* known_rowptr, const int32_t* known_col, float* lse, void* ws, size_t ws_bytes,
+                          void* stream);
+int hgin_link_lse_bwd_src_f32(const int64_t* src, int64_t n_query, int64_t n_src, int64_t n_dst, const float* z_src,
+                              int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F, float inv_t,
+                              const int32_t* known_rowptr, const int32_t* known_col, const float* lse, const float* g,
+                              float* g_src, int64_t ld_gsrc, void* ws, size_t ws_bytes, void* stream);
+int hgin_link_lse_bwd_dst_f32(const int64_t* src, int64_t n_query, int64_t n_src, int64_t n_dst, const float* z_src,
+                              int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F, float inv_t,
+                              const int32_t* known_rowptr, const int32_t* known_col, const float* lse, const float* g,
+                              float* g_dst, int64_t ld_gdst, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- F4 widening: HetroGAT's graph attention (models.py:380-506, PyG 2.0.2 GATConv) ---------------------------
  * x_s / x_d: projected source / destination features [N, H * C] (row stride ld*), edges = the relation after
  * GATConv's self-loop handling, as CSR by destination (rowptr, col) and CSC by source (cptr, cdst, cpos = the CSR
