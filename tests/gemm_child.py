@@ -2,7 +2,8 @@
 of the weight-stationary kernel (K 128 / 256 / 512, N 128 / 256; ragged M, M below one block, many blocks
 per workgroup; accum / z present or not; a two-source A) under the process-static HGIN_* switches its parent
 set, and the fp32 forward GEMM at the shapes of its weight-stationary kernel (k_ws_f32).  Also the dX GEMMs (plain
-and combine) and the weight-gradient GEMMs.  Checks every output against an fp32 / fp64 evaluation of the same
+and combine) and the weight-gradient GEMMs, and the weight-stationary NT forms at row counts relative to the launch grid
+(grid_cases: workgroups that own 2, 3 and 4 blocks).  Checks every output against an fp32 / fp64 evaluation of the same
 operands and saves them, so the parent can compare switch settings.
 
     python tests/gemm_child.py OUT.pt
@@ -225,6 +226,24 @@ def run_dw(M, N, K, k1, dt=BF, *, g):
     return {"tol_dw": out.cpu()}
 
 
+def grid_cases():
+    """Row counts relative to the launch grid (tests/test_gpu_ws_tail.py): 2 Gw + 1 and 3 Gw + 1 blocks of BM rows, the
+    last one 5 rows, so workgroup 0 runs 3 / 4 blocks and the others 2 / 3.  Gw = the CU count G, or 2 G where two
+    workgroups share a CU (bf16 K = 128, N = 256 without accum: 64-row blocks).  {key: (runner, arguments)}."""
+    G = torch.cuda.get_device_properties(0).multi_processor_count
+    cases = {}
+    for n in (2, 3):
+        m32, m64 = 32 * n * G + 5, 64 * n * 2 * G + 5
+        cases[f"grid{n}_f32"] = (run_f32, (m32, 256, 256, True, True))
+        cases[f"grid{n}_f32cat"] = (run_f32_concat, (m32, False, True, 0.37, False))
+        cases[f"grid{n}_dxf32p"] = (run_dx_f32_plain, (m32, 128, False))
+        cases[f"grid{n}_dxf32_prev"] = (run_dx_f32, (m32, True, True))
+        cases[f"grid{n}_dxf32"] = (run_dx_f32, (m32, True, False))
+        cases[f"grid{n}_bf16"] = (run, (m32, 256, 256, True, True, 0))
+        cases[f"grid{n}_bf16_k128"] = (run, (m64, 128, 256, False, False, 0))
+    return cases
+
+
 def main():
     torch.cuda.init()
     g = torch.Generator(device="cuda").manual_seed(7)
@@ -235,6 +254,7 @@ def main():
     res.update({f"dxf32{c}": run_dx_f32(*c, g=g) for c in DX_F32_CASES})
     res.update({f"dxf32p{c}": run_dx_f32_plain(*c, g=g) for c in DX_F32_PLAIN_CASES})
     res.update({f"dw{c}": run_dw(*c, g=g) for c in DW_CASES})
+    res.update({k: fn(*c, g=g) for k, (fn, c) in grid_cases().items()})   # (last: the draws of the cases above stay)
     torch.save(res, sys.argv[1])
     print("gemm child ok", {k: v for k, v in os.environ.items() if k.startswith("HGIN_")}, flush=True)
 
