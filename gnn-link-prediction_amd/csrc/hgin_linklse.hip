@@ -28,6 +28,11 @@
 // keeps, per query column, a cursor into its source's sorted known row: opened by a lower-bound search at the first
 // tile, advanced over the entries that fall into the current tile, which set bits for those among the 32 destination
 // rows the lane holds.  With an average degree of about 6 this is cold code beside the MFMAs.
+//
+// A24 — the same three calls over graph-local candidates (include/hgin.h A24): cand(q) lies inside A19's segment of
+// src[q].  Separate instantiations (SEG) of k_lse_sweep and k_lse_bwd: the query-stationary ones sweep only the tiles
+// their block's segments cover (seg_tile_slice), the tile-stationary one skips the query blocks whose covered range
+// (k_lse_blk_range) misses its tile.  The unsegmented instantiations keep their launches, traces and bits.
 #include <cmath>
 
 #include "hgin_linkscore.h"   // the K order, ld_k4, mfma_k8, the tile constants and the split plan (shared with A15 / A16)
@@ -95,32 +100,56 @@ __device__ __forceinline__ void lse_join(float& m, float& s, float m2, float s2)
 // k_rank_sweep's geometry: workgroup = 4 waves as 2 x 2, each 64 destinations x 64 queries; in an accumulator block
 // lane (li, lh) holds query column li and the destination rows 8 (v / 4) + 4 lh + v % 4.  blockIdx.x = split *
 // n_qblocks + query block.  part[split * Q + q] = (max, sum) of the split's candidates of query q.
-template <bool VEC>
+// A24 (SEG): a lane sums a destination only inside its query column's segment [lo, lo + n), and the workgroup's splits
+// cut the tiles its 128 queries' segments cover (seg_tile_slice; tiles_per_split / n_tiles are then unused, `splits`
+// is).  A slice may be empty; k_lse_merge reads every split, so it still writes its (-inf, 0).
+template <bool VEC, bool SEG = false>
 __global__ __launch_bounds__(256, 2) void k_lse_sweep(const int64_t* __restrict__ src, int64_t Q, int64_t n_src,
                                                       int64_t n_dst, const float* __restrict__ zs, int64_t lds_,
                                                       const float* __restrict__ zd, int64_t ldd, int F, float inv_t,
                                                       const int32_t* __restrict__ rowptr,
                                                       const int32_t* __restrict__ col, float2* __restrict__ part,
-                                                      int64_t n_qblocks, int64_t tiles_per_split, int64_t n_tiles) {
+                                                      int64_t n_qblocks, int64_t tiles_per_split, int64_t n_tiles,
+                                                      int64_t splits = 1, const int32_t* __restrict__ src_seg = nullptr,
+                                                      const int32_t* __restrict__ dst_ptr = nullptr, int n_graphs = 1) {
   __shared__ __attribute__((aligned(16))) float As[kRankTile * kRankRow];   // destinations
   __shared__ __attribute__((aligned(16))) float Bs[kRankTile * kRankRow];   // queries
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5, wm = wave >> 1, wn = wave & 1;
   const int64_t qb = (int64_t)blockIdx.x % n_qblocks, split = (int64_t)blockIdx.x / n_qblocks;
   const int64_t q0 = qb * kRankTile;
-  const int64_t t_beg = split * tiles_per_split;
-  const int64_t t_end = t_beg + tiles_per_split < n_tiles ? t_beg + tiles_per_split : n_tiles;
-  if (t_beg >= t_end) return;
+  int64_t t_beg = split * tiles_per_split;
+  int64_t t_end = t_beg + tiles_per_split < n_tiles ? t_beg + tiles_per_split : n_tiles;
+  if constexpr (!SEG)
+    if (t_beg >= t_end) return;
 
   // this lane's query columns
   float m[2] = {-INFINITY, -INFINITY}, s[2] = {0.0f, 0.0f};
   int64_t qcol[2];
+  uint32_t slo[2] = {0u, 0u}, sn[2] = {0u, 0u};
   KnownCursor kc[2];
 #pragma unroll
   for (int tn = 0; tn < 2; ++tn) {
     qcol[tn] = q0 + wn * 64 + tn * 32 + li;
     const int64_t q = qcol[tn] < Q ? qcol[tn] : Q - 1;
-    known_open(kc[tn], rowptr, col, clamp_id(src[q], n_src), t_beg * kRankTile);
+    if constexpr (SEG) seg_range(src_seg, dst_ptr, n_graphs, clamp_id(src[q], n_src), n_dst, slo[tn], sn[tn]);
+    else known_open(kc[tn], rowptr, col, clamp_id(src[q], n_src), t_beg * kRankTile);
+  }
+  if constexpr (SEG) {
+    seg_tile_slice(slo, sn, split, splits, t_beg, t_end);
+    if (t_beg >= t_end) {   // block-uniform: nothing of this split is a candidate
+      if (lh == 0 && wm == 0) {
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn)
+          if (qcol[tn] < Q) part[split * Q + qcol[tn]] = make_float2(-INFINITY, 0.0f);
+      }
+      return;
+    }
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn) {
+      const int64_t q = qcol[tn] < Q ? qcol[tn] : Q - 1;
+      known_open(kc[tn], rowptr, col, clamp_id(src[q], n_src), t_beg * kRankTile);
+    }
   }
 
   // staging as k_rank_sweep: thread (r = tid / 8, kq = tid % 8) moves features 4 kq .. 4 kq + 3 of rows r + 32 i; rows
@@ -189,7 +218,8 @@ __global__ __launch_bounds__(256, 2) void k_lse_sweep(const int64_t* __restrict_
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
           const int64_t c = cbase + tm * 32 + 8 * (v >> 2) + (v & 3);
-          const bool ok = c < n_dst && ((km[tn] >> (16 * tm + v)) & 1u) == 0u;
+          bool ok = c < n_dst && ((km[tn] >> (16 * tm + v)) & 1u) == 0u;
+          if constexpr (SEG) ok = ok && (uint32_t)c - slo[tn] < sn[tn];   // unsigned: slo <= c < slo + sn
           const float t = ok ? acc[tm][tn][v] * inv_t : -INFINITY;
           acc[tm][tn][v] = t;
           mx = fmaxf(mx, t);
@@ -252,7 +282,12 @@ __global__ __launch_bounds__(256) void k_lse_merge(const float2* __restrict__ pa
 // part = NULL: one split, rows go straight to out (SRC: row src[q]); else part[(split * rows + row) * F + f].
 // One workgroup per CU (no scratch): at NU = 2 the two accumulator sets of 64, the prefetched stage and the second
 // product's rows spill 50 .. 56 VGPRs when the kernel is held to the 256 registers of two per CU.
-template <bool VEC, bool DST, int NU>
+// A24 (SEG): W is also 0 outside the query column's segment.  SRC: the swept tiles are this split's slice of the tiles
+// the block's segments cover (seg_tile_slice); an empty slice sweeps nothing and still writes its zeros (k_lse_fold
+// adds every split).  DST: the plan's query blocks are swept, but a block whose covered range blk_rng[qb] = [lo, hi)
+// (k_lse_blk_range) misses this tile is skipped whole, workgroup-uniformly, and the prefetch looks for the next block
+// that is not; a tile every block skips writes zeros (g_dst is not cleared by the caller).
+template <bool VEC, bool DST, int NU, bool SEG = false>
 __global__ __launch_bounds__(256, 1) void k_lse_bwd(const int64_t* __restrict__ src, int64_t Q, int64_t n_src,
                                                     int64_t n_dst, const float* __restrict__ zs, int64_t lds_,
                                                     const float* __restrict__ zd, int64_t ldd, int F, float inv_t,
@@ -260,7 +295,10 @@ __global__ __launch_bounds__(256, 1) void k_lse_bwd(const int64_t* __restrict__ 
                                                     const int32_t* __restrict__ col, const float* __restrict__ lse,
                                                     const float* __restrict__ g, float* __restrict__ out, int64_t ldo,
                                                     float* __restrict__ part, int64_t n_stat, int64_t per_split,
-                                                    int64_t n_sweep, int64_t splits) {
+                                                    int64_t n_sweep, int64_t splits,
+                                                    const int32_t* __restrict__ src_seg = nullptr,
+                                                    const int32_t* __restrict__ dst_ptr = nullptr, int n_graphs = 1,
+                                                    const int2* __restrict__ blk_rng = nullptr) {
   constexpr int FC = 64 * NU;     // output features of this workgroup
   constexpr int ZROW = FC + 4;    // LDS row stride of the second product's 32 embedding rows
   __shared__ __attribute__((aligned(16))) float As[kRankTile * kRankRow];   // destinations
@@ -272,14 +310,23 @@ __global__ __launch_bounds__(256, 1) void k_lse_bwd(const int64_t* __restrict__ 
   const int64_t rest = (int64_t)blockIdx.x / n_stat;
   const int64_t split = rest % splits;
   const int f0 = (int)(rest / splits) * FC;
-  const int64_t it_beg = split * per_split;
-  const int64_t it_end = it_beg + per_split < n_sweep ? it_beg + per_split : n_sweep;
-  if (it_beg >= it_end) return;
+  int64_t it_beg = split * per_split;
+  int64_t it_end = it_beg + per_split < n_sweep ? it_beg + per_split : n_sweep;
+  if constexpr (!SEG || DST)
+    if (it_beg >= it_end) return;
 
   // this lane's query columns: g * inv_t, lse, whether the column counts, the cursor into the known row
   float gq[2], lq[2];
   bool qok[2];
   KnownCursor kc[2];
+  uint32_t slo[2] = {0u, 0u}, sn[2] = {0u, 0u};   // SEG: the columns' segments
+  auto open_segs = [&](int64_t qb) {
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn) {
+      const int64_t qc = qb * kRankTile + wn * 64 + tn * 32 + li;
+      seg_range(src_seg, dst_ptr, n_graphs, clamp_id(src[qc < Q ? qc : Q - 1], n_src), n_dst, slo[tn], sn[tn]);
+    }
+  };
   auto open_cols = [&](int64_t qb, int64_t tile) {
 #pragma unroll
     for (int tn = 0; tn < 2; ++tn) {
@@ -290,7 +337,24 @@ __global__ __launch_bounds__(256, 1) void k_lse_bwd(const int64_t* __restrict__ 
       qok[tn] = qc < Q && lq[tn] > -INFINITY;
       known_open(kc[tn], rowptr, col, clamp_id(src[q], n_src), tile * kRankTile);
     }
+    if constexpr (SEG && DST) open_segs(qb);
   };
+  // SEG, DST: the first query block at or after `it` whose covered destinations touch this tile (it_end: none)
+  auto next_live = [&](int64_t it) -> int64_t {
+    if constexpr (SEG && DST) {
+      const int64_t c_lo = stat * kRankTile, c_hi = c_lo + kRankTile;
+      for (; it < it_end; ++it) {
+        const int2 r = blk_rng[it];
+        if ((int64_t)r.x < c_hi && (int64_t)r.y > c_lo) break;
+      }
+    }
+    return it;
+  };
+  if constexpr (SEG && !DST) {
+    open_segs(stat);
+    seg_tile_slice(slo, sn, split, splits, it_beg, it_end);   // may be empty: the zeros below are still written
+  }
+  if constexpr (SEG && DST) it_beg = next_live(it_beg);
 
   const int lr = tid >> 3, lk = (tid & 7) * 4;
   const float* arow[4];
@@ -321,11 +385,14 @@ __global__ __launch_bounds__(256, 1) void k_lse_bwd(const int64_t* __restrict__ 
 
   f32x16 acc2[2][NU];
   zero_acc(acc2);
-  set_a(DST ? stat : it_beg);
-  set_b(DST ? it_beg : stat);
-  load_stage(0);
-  if constexpr (!DST) open_cols(stat, it_beg);
-  for (int64_t it = it_beg; it < it_end; ++it) {
+  if (!SEG || it_beg < it_end) {   // block-uniform
+    set_a(DST ? stat : it_beg);
+    set_b(DST ? it_beg : stat);
+    load_stage(0);
+    if constexpr (!DST) open_cols(stat, it_beg);
+  }
+  for (int64_t it = it_beg, nxt; it < it_end; it = nxt) {
+    nxt = next_live(it + 1);
     const int64_t tile = DST ? stat : it, qb = DST ? it : stat;
     const int64_t c0 = tile * kRankTile;
     if constexpr (DST) open_cols(qb, tile);
@@ -344,9 +411,9 @@ __global__ __launch_bounds__(256, 1) void k_lse_bwd(const int64_t* __restrict__ 
       __syncthreads();
       if (kc_ + 1 < nk) {
         load_stage(kc_ + 1);
-      } else if (it + 1 < it_end) {
-        if constexpr (DST) set_b(it + 1);
-        else set_a(it + 1);
+      } else if (nxt < it_end) {
+        if constexpr (DST) set_b(nxt);
+        else set_a(nxt);
         load_stage(0);
       }
       __builtin_amdgcn_s_setprio(1);
@@ -374,7 +441,8 @@ __global__ __launch_bounds__(256, 1) void k_lse_bwd(const int64_t* __restrict__ 
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
           const int64_t c = cbase + tm * 32 + 8 * (v >> 2) + (v & 3);
-          const bool ok = qok[tn] && c < n_dst && ((km[tn] >> (16 * tm + v)) & 1u) == 0u;
+          bool ok = qok[tn] && c < n_dst && ((km[tn] >> (16 * tm + v)) & 1u) == 0u;
+          if constexpr (SEG) ok = ok && (uint32_t)c - slo[tn] < sn[tn];   // unsigned: slo <= c < slo + sn
           const float t = acc[tm][tn][v] * inv_t;
           acc[tm][tn][v] = ok ? gq[tn] * expf(t - lq[tn]) : 0.0f;
         }
@@ -469,9 +537,35 @@ __global__ __launch_bounds__(256) void k_lse_fold(const float* __restrict__ part
   out[row * ldo + f] = acc;
 }
 
+// A24: rng[qb] = [min lo, max hi) over the non-empty segments of query block qb's queries; (INT_MAX, 0) when it has
+// none.  One workgroup of 128 threads per query block.
+__global__ __launch_bounds__(kRankTile) void k_lse_blk_range(const int64_t* __restrict__ src, int64_t Q, int64_t n_src,
+                                                              int64_t n_dst, const int32_t* __restrict__ src_seg,
+                                                              const int32_t* __restrict__ dst_ptr, int n_graphs,
+                                                              int2* __restrict__ rng) {
+  __shared__ int s_lo, s_hi;
+  if (threadIdx.x == 0) {
+    s_lo = 0x7fffffff;
+    s_hi = 0;
+  }
+  __syncthreads();
+  const int64_t q = (int64_t)blockIdx.x * kRankTile + threadIdx.x;
+  if (q < Q) {
+    uint32_t lo, n;
+    seg_range(src_seg, dst_ptr, n_graphs, clamp_id(src[q], n_src), n_dst, lo, n);
+    if (n != 0u) {
+      atomicMin(&s_lo, (int)lo);
+      atomicMax(&s_hi, (int)(lo + n));
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) rng[blockIdx.x] = make_int2(s_lo, s_hi);
+}
+
 struct LsePlans {
   SweepPlan fwd, dst;   // fwd also cuts bwd_src (query-stationary); dst: destination tiles stationary, query blocks swept
   size_t fwd_bytes, src_bytes, dst_bytes;
+  size_t rng_bytes;     // A24: the query blocks' covered ranges, behind the partials of the segmented bwd_dst
 };
 LsePlans lse_plans(int64_t Q, int64_t n_dst, int64_t F) {
   LsePlans p;
@@ -480,6 +574,7 @@ LsePlans lse_plans(int64_t Q, int64_t n_dst, int64_t F) {
   p.fwd_bytes = align_up((size_t)p.fwd.splits * (size_t)Q * sizeof(float2), 256);
   p.src_bytes = p.fwd.splits > 1 ? align_up((size_t)p.fwd.splits * (size_t)Q * (size_t)F * sizeof(float), 256) : 0;
   p.dst_bytes = p.dst.splits > 1 ? align_up((size_t)p.dst.splits * (size_t)n_dst * (size_t)F * sizeof(float), 256) : 0;
+  p.rng_bytes = align_up((size_t)p.fwd.n_qblocks * sizeof(int2), 256);
   return p;
 }
 
@@ -525,11 +620,79 @@ int lse_check_ws(const char* what, const void* ws, size_t ws_bytes, size_t need)
   return HGIN_OK;
 }
 
-// both gradients behind one set of checks and launches
+// A24's additional arguments
+int lse_check_seg(const char* what, const int32_t* src_seg, const int32_t* dst_ptr, int64_t n_graphs) {
+  HGIN_ARG_CHECK(src_seg != nullptr, "%s: src_seg NULL", what);
+  HGIN_ARG_CHECK(dst_ptr != nullptr, "%s: dst_ptr NULL", what);
+  HGIN_ARG_CHECK(n_graphs >= 1 && n_graphs < (int64_t(1) << 31), "%s: n_graphs = %lld must be in [1, 2^31)", what,
+                 (long long)n_graphs);
+  return HGIN_OK;
+}
+
+size_t lse_workspace(const LsePlans& p, bool seg) {
+  size_t need = p.fwd_bytes;
+  if (p.src_bytes > need) need = p.src_bytes;
+  const size_t dst = p.dst_bytes + (seg ? p.rng_bytes : 0);
+  if (dst > need) need = dst;
+  return need;
+}
+
+// A23 (src_seg = NULL) and A24 behind one set of checks and launches
+int lse_fwd_impl(const char* what, const int64_t* src, int64_t Q, int64_t n_src, int64_t n_dst, const float* z_src,
+                 int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F, float inv_t,
+                 const int32_t* known_rowptr, const int32_t* known_col, float* lse, void* ws, size_t ws_bytes,
+                 const int32_t* src_seg, const int32_t* dst_ptr, int n_graphs, void* stream) {
+  const bool seg = src_seg != nullptr;
+  int rc = lse_check_operands(what, src, Q, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, F, inv_t, known_rowptr,
+                              known_col);
+  if (rc != HGIN_OK) return rc;
+  HGIN_ARG_CHECK(lse != nullptr, "%s: lse NULL", what);
+  const LsePlans plans = lse_plans(Q, n_dst, F);
+  const SweepPlan plan = plans.fwd;
+  HGIN_ARG_CHECK(plan.n_qblocks * plan.splits < (int64_t(1) << 31), "%s: too many workgroups", what);
+  rc = lse_check_ws(what, ws, ws_bytes, plans.fwd_bytes);
+  if (rc != HGIN_OK) return rc;
+  hipStream_t s = as_stream(stream);
+  const bool vec = F % 4 == 0 && aligned16(z_src) && aligned16(z_dst) && ld_src % 4 == 0 && ld_dst % 4 == 0;
+  float2* part = static_cast<float2*>(ws);
+  const unsigned grid = (unsigned)(plan.n_qblocks * plan.splits);
+  if (seg) {
+    HGIN_TRACE("k_lse_sweep<%d,SEG> splits=%lld sweep=%lld", vec ? 4 : 1, (long long)plan.splits,
+               (long long)plan.tiles_per_split);
+    if (vec)
+      k_lse_sweep<true, true><<<grid, 256, 0, s>>>(src, Q, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, (int)F, inv_t,
+                                                   known_rowptr, known_col, part, plan.n_qblocks,
+                                                   plan.tiles_per_split, plan.n_tiles, plan.splits, src_seg, dst_ptr,
+                                                   n_graphs);
+    else
+      k_lse_sweep<false, true><<<grid, 256, 0, s>>>(src, Q, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, (int)F, inv_t,
+                                                    known_rowptr, known_col, part, plan.n_qblocks,
+                                                    plan.tiles_per_split, plan.n_tiles, plan.splits, src_seg, dst_ptr,
+                                                    n_graphs);
+  } else {
+    HGIN_TRACE("k_lse_sweep<%d> splits=%lld sweep=%lld", vec ? 4 : 1, (long long)plan.splits,
+               (long long)plan.tiles_per_split);
+    if (vec)
+      k_lse_sweep<true><<<grid, 256, 0, s>>>(src, Q, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, (int)F, inv_t,
+                                             known_rowptr, known_col, part, plan.n_qblocks, plan.tiles_per_split,
+                                             plan.n_tiles);
+    else
+      k_lse_sweep<false><<<grid, 256, 0, s>>>(src, Q, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, (int)F, inv_t,
+                                              known_rowptr, known_col, part, plan.n_qblocks, plan.tiles_per_split,
+                                              plan.n_tiles);
+  }
+  HGIN_TRACE("k_lse_merge splits=%lld", (long long)plan.splits);
+  k_lse_merge<<<(unsigned)ceil_div(Q, 256), 256, 0, s>>>(part, Q, plan.splits, lse);
+  return check_launch(what);
+}
+
+// both gradients, A23 (src_seg = NULL) and A24, behind one set of checks and launches
 int lse_bwd_impl(const char* what, bool dst, const int64_t* src, int64_t Q, int64_t n_src, int64_t n_dst,
                  const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F, float inv_t,
                  const int32_t* known_rowptr, const int32_t* known_col, const float* lse, const float* g, float* out,
-                 int64_t ldo, void* ws, size_t ws_bytes, void* stream) {
+                 int64_t ldo, void* ws, size_t ws_bytes, const int32_t* src_seg, const int32_t* dst_ptr, int n_graphs,
+                 void* stream) {
+  const bool seg = src_seg != nullptr;
   int rc = lse_check_operands(what, src, Q, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, F, inv_t, known_rowptr,
                               known_col);
   if (rc != HGIN_OK) return rc;
@@ -542,7 +705,8 @@ int lse_bwd_impl(const char* what, bool dst, const int64_t* src, int64_t Q, int6
   const int64_t chunks = ceil_div(F, lse_feature_chunk(F));
   const int64_t grid = plan.n_qblocks * plan.splits * chunks;
   HGIN_ARG_CHECK(grid < (int64_t(1) << 31), "%s: %lld workgroups exceed 2^31", what, (long long)grid);
-  rc = lse_check_ws(what, ws, ws_bytes, dst ? plans.dst_bytes : plans.src_bytes);
+  const size_t part_bytes = dst ? plans.dst_bytes : plans.src_bytes;
+  rc = lse_check_ws(what, ws, ws_bytes, part_bytes + (seg && dst ? plans.rng_bytes : 0));
   if (rc != HGIN_OK) return rc;
   hipStream_t s = as_stream(stream);
   const bool vec = F % 4 == 0 && aligned16(z_src) && aligned16(z_dst) && ld_src % 4 == 0 && ld_dst % 4 == 0;
@@ -554,13 +718,28 @@ int lse_bwd_impl(const char* what, bool dst, const int64_t* src, int64_t Q, int6
       return static_cast<int>(e);
     }
   }
-  HGIN_TRACE("k_lse_bwd<%d,%s> splits=%lld sweep=%lld chunks=%lld", vec ? 4 : 1, dst ? "DST" : "SRC",
-             (long long)plan.splits, (long long)plan.tiles_per_split, (long long)chunks);
-#define HGIN_LSE_BWD_NU(VEC_, DST_, NU_)                                                                             \
-  k_lse_bwd<VEC_, DST_, NU_><<<(unsigned)grid, 256, 0, s>>>(src, Q, n_src, n_dst, z_src, ld_src, z_dst, ld_dst,      \
-                                                            (int)F, inv_t, known_rowptr, known_col, lse, g, out, ldo, \
-                                                            part, plan.n_qblocks, plan.tiles_per_split, plan.n_tiles, \
-                                                            plan.splits)
+  int2* rng = nullptr;
+  if (seg && dst) {   // the query blocks' covered ranges, behind the partials
+    rng = reinterpret_cast<int2*>(static_cast<char*>(ws) + part_bytes);
+    HGIN_TRACE("k_lse_blk_range blocks=%lld", (long long)plans.fwd.n_qblocks);
+    k_lse_blk_range<<<(unsigned)plans.fwd.n_qblocks, kRankTile, 0, s>>>(src, Q, n_src, n_dst, src_seg, dst_ptr,
+                                                                         n_graphs, rng);
+  }
+  HGIN_TRACE("k_lse_bwd<%d,%s%s> splits=%lld sweep=%lld chunks=%lld", vec ? 4 : 1, dst ? "DST" : "SRC",
+             seg ? ",SEG" : "", (long long)plan.splits, (long long)plan.tiles_per_split, (long long)chunks);
+#define HGIN_LSE_BWD_NU(VEC_, DST_, NU_)                                                                              \
+  do {                                                                                                                \
+    if (seg)                                                                                                          \
+      k_lse_bwd<VEC_, DST_, NU_, true><<<(unsigned)grid, 256, 0, s>>>(                                                \
+          src, Q, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, (int)F, inv_t, known_rowptr, known_col, lse, g, out,    \
+          ldo, part, plan.n_qblocks, plan.tiles_per_split, plan.n_tiles, plan.splits, src_seg, dst_ptr, n_graphs,     \
+          rng);                                                                                                       \
+    else                                                                                                              \
+      k_lse_bwd<VEC_, DST_, NU_><<<(unsigned)grid, 256, 0, s>>>(src, Q, n_src, n_dst, z_src, ld_src, z_dst, ld_dst,   \
+                                                                (int)F, inv_t, known_rowptr, known_col, lse, g, out,  \
+                                                                ldo, part, plan.n_qblocks, plan.tiles_per_split,      \
+                                                                plan.n_tiles, plan.splits);                           \
+  } while (0)
 #define HGIN_LSE_BWD(VEC_, DST_)                 \
   do {                                           \
     if (F > 128) HGIN_LSE_BWD_NU(VEC_, DST_, 4); \
@@ -594,11 +773,7 @@ extern "C" int hgin_link_lse_workspace_size(int64_t n_query, int64_t n_dst, int6
   HGIN_ARG_CHECK(bytes != nullptr, "%s: bytes is NULL", what);
   const int rc = lse_check_shapes(what, n_query, n_dst, F);
   if (rc != HGIN_OK) return rc;
-  const LsePlans p = lse_plans(n_query, n_dst, F);
-  size_t need = p.fwd_bytes;
-  if (p.src_bytes > need) need = p.src_bytes;
-  if (p.dst_bytes > need) need = p.dst_bytes;
-  *bytes = need;
+  *bytes = lse_workspace(lse_plans(n_query, n_dst, F), false);
   return HGIN_OK;
 }
 
@@ -606,34 +781,8 @@ extern "C" int hgin_link_lse_fwd_f32(const int64_t* src, int64_t n_query, int64_
                                      const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F,
                                      float inv_t, const int32_t* known_rowptr, const int32_t* known_col, float* lse,
                                      void* ws, size_t ws_bytes, void* stream) {
-  const char* what = "hgin_link_lse_fwd_f32";
-  const int64_t Q = n_query;
-  int rc = lse_check_operands(what, src, Q, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, F, inv_t, known_rowptr,
-                              known_col);
-  if (rc != HGIN_OK) return rc;
-  HGIN_ARG_CHECK(lse != nullptr, "%s: lse NULL", what);
-  const LsePlans plans = lse_plans(Q, n_dst, F);
-  const SweepPlan plan = plans.fwd;
-  HGIN_ARG_CHECK(plan.n_qblocks * plan.splits < (int64_t(1) << 31), "%s: too many workgroups", what);
-  rc = lse_check_ws(what, ws, ws_bytes, plans.fwd_bytes);
-  if (rc != HGIN_OK) return rc;
-  hipStream_t s = as_stream(stream);
-  const bool vec = F % 4 == 0 && aligned16(z_src) && aligned16(z_dst) && ld_src % 4 == 0 && ld_dst % 4 == 0;
-  float2* part = static_cast<float2*>(ws);
-  const unsigned grid = (unsigned)(plan.n_qblocks * plan.splits);
-  HGIN_TRACE("k_lse_sweep<%d> splits=%lld sweep=%lld", vec ? 4 : 1, (long long)plan.splits,
-             (long long)plan.tiles_per_split);
-  if (vec)
-    k_lse_sweep<true><<<grid, 256, 0, s>>>(src, Q, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, (int)F, inv_t,
-                                           known_rowptr, known_col, part, plan.n_qblocks, plan.tiles_per_split,
-                                           plan.n_tiles);
-  else
-    k_lse_sweep<false><<<grid, 256, 0, s>>>(src, Q, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, (int)F, inv_t,
-                                            known_rowptr, known_col, part, plan.n_qblocks, plan.tiles_per_split,
-                                            plan.n_tiles);
-  HGIN_TRACE("k_lse_merge splits=%lld", (long long)plan.splits);
-  k_lse_merge<<<(unsigned)ceil_div(Q, 256), 256, 0, s>>>(part, Q, plan.splits, lse);
-  return check_launch(what);
+  return lse_fwd_impl("hgin_link_lse_fwd_f32", src, n_query, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, F, inv_t,
+                      known_rowptr, known_col, lse, ws, ws_bytes, nullptr, nullptr, 1, stream);
 }
 
 extern "C" int hgin_link_lse_bwd_src_f32(const int64_t* src, int64_t n_query, int64_t n_src, int64_t n_dst,
@@ -642,7 +791,8 @@ extern "C" int hgin_link_lse_bwd_src_f32(const int64_t* src, int64_t n_query, in
                                          const float* lse, const float* g, float* g_src, int64_t ld_gsrc, void* ws,
                                          size_t ws_bytes, void* stream) {
   return lse_bwd_impl("hgin_link_lse_bwd_src_f32", false, src, n_query, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, F,
-                      inv_t, known_rowptr, known_col, lse, g, g_src, ld_gsrc, ws, ws_bytes, stream);
+                      inv_t, known_rowptr, known_col, lse, g, g_src, ld_gsrc, ws, ws_bytes, nullptr, nullptr, 1,
+                      stream);
 }
 
 extern "C" int hgin_link_lse_bwd_dst_f32(const int64_t* src, int64_t n_query, int64_t n_src, int64_t n_dst,
@@ -651,5 +801,54 @@ extern "C" int hgin_link_lse_bwd_dst_f32(const int64_t* src, int64_t n_query, in
                                          const float* lse, const float* g, float* g_dst, int64_t ld_gdst, void* ws,
                                          size_t ws_bytes, void* stream) {
   return lse_bwd_impl("hgin_link_lse_bwd_dst_f32", true, src, n_query, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, F,
-                      inv_t, known_rowptr, known_col, lse, g, g_dst, ld_gdst, ws, ws_bytes, stream);
+                      inv_t, known_rowptr, known_col, lse, g, g_dst, ld_gdst, ws, ws_bytes, nullptr, nullptr, 1,
+                      stream);
+}
+
+// ---- A24: the same three calls over graph-local candidates ------------------------------------------------------------
+extern "C" int hgin_link_lse_seg_workspace_size(int64_t n_query, int64_t n_dst, int64_t F, size_t* bytes) {
+  const char* what = "hgin_link_lse_seg_workspace_size";
+  HGIN_ARG_CHECK(bytes != nullptr, "%s: bytes is NULL", what);
+  const int rc = lse_check_shapes(what, n_query, n_dst, F);
+  if (rc != HGIN_OK) return rc;
+  *bytes = lse_workspace(lse_plans(n_query, n_dst, F), true);
+  return HGIN_OK;
+}
+
+extern "C" int hgin_link_lse_fwd_seg_f32(const int64_t* src, int64_t n_query, int64_t n_src, int64_t n_dst,
+                                         const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst,
+                                         int64_t F, float inv_t, const int32_t* known_rowptr, const int32_t* known_col,
+                                         float* lse, void* ws, size_t ws_bytes, const int32_t* src_seg,
+                                         const int32_t* dst_ptr, int64_t n_graphs, void* stream) {
+  const char* what = "hgin_link_lse_fwd_seg_f32";
+  const int rc = lse_check_seg(what, src_seg, dst_ptr, n_graphs);
+  if (rc != HGIN_OK) return rc;
+  return lse_fwd_impl(what, src, n_query, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, F, inv_t, known_rowptr,
+                      known_col, lse, ws, ws_bytes, src_seg, dst_ptr, (int)n_graphs, stream);
+}
+
+extern "C" int hgin_link_lse_bwd_src_seg_f32(const int64_t* src, int64_t n_query, int64_t n_src, int64_t n_dst,
+                                             const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst,
+                                             int64_t F, float inv_t, const int32_t* known_rowptr,
+                                             const int32_t* known_col, const float* lse, const float* g, float* g_src,
+                                             int64_t ld_gsrc, void* ws, size_t ws_bytes, const int32_t* src_seg,
+                                             const int32_t* dst_ptr, int64_t n_graphs, void* stream) {
+  const char* what = "hgin_link_lse_bwd_src_seg_f32";
+  const int rc = lse_check_seg(what, src_seg, dst_ptr, n_graphs);
+  if (rc != HGIN_OK) return rc;
+  return lse_bwd_impl(what, false, src, n_query, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, F, inv_t, known_rowptr,
+                      known_col, lse, g, g_src, ld_gsrc, ws, ws_bytes, src_seg, dst_ptr, (int)n_graphs, stream);
+}
+
+extern "C" int hgin_link_lse_bwd_dst_seg_f32(const int64_t* src, int64_t n_query, int64_t n_src, int64_t n_dst,
+                                             const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst,
+                                             int64_t F, float inv_t, const int32_t* known_rowptr,
+                                             const int32_t* known_col, const float* lse, const float* g, float* g_dst,
+                                             int64_t ld_gdst, void* ws, size_t ws_bytes, const int32_t* src_seg,
+                                             const int32_t* dst_ptr, int64_t n_graphs, void* stream) {
+  const char* what = "hgin_link_lse_bwd_dst_seg_f32";
+  const int rc = lse_check_seg(what, src_seg, dst_ptr, n_graphs);
+  if (rc != HGIN_OK) return rc;
+  return lse_bwd_impl(what, true, src, n_query, n_src, n_dst, z_src, ld_src, z_dst, ld_dst, F, inv_t, known_rowptr,
+                      known_col, lse, g, g_dst, ld_gdst, ws, ws_bytes, src_seg, dst_ptr, (int)n_graphs, stream);
 }

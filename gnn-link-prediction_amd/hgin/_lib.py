@@ -219,6 +219,13 @@ _SIGS = {
                                    _I64, _P, _SZ, _P], _I32),
     "hgin_link_lse_bwd_dst_f32": ([_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _I64, ctypes.c_float, _P, _P, _P, _P, _P,
                                    _I64, _P, _SZ, _P], _I32),
+    "hgin_link_lse_seg_workspace_size": ([_I64, _I64, _I64, ctypes.POINTER(_SZ)], _I32),
+    "hgin_link_lse_fwd_seg_f32": ([_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _I64, ctypes.c_float, _P, _P, _P, _P, _SZ,
+                                   _P, _P, _I64, _P], _I32),
+    "hgin_link_lse_bwd_src_seg_f32": ([_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _I64, ctypes.c_float, _P, _P, _P, _P,
+                                       _P, _I64, _P, _SZ, _P, _P, _I64, _P], _I32),
+    "hgin_link_lse_bwd_dst_seg_f32": ([_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _I64, ctypes.c_float, _P, _P, _P, _P,
+                                       _P, _I64, _P, _SZ, _P, _P, _I64, _P], _I32),
     "hgin_aggregate_long_f32": ([_P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I32, _P, _I64, _P,
                                  _SZ, _P], _I32),
     "hgin_aggregate_long_bf16": ([_P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I32, _P, _I64, _P,

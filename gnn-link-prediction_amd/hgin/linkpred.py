@@ -50,7 +50,8 @@ Full softmax (A23, not in the reference): ``link_lse`` is the log-sum-exp of a s
 (known edges masked), forward and backward on the matrix cores without a score matrix (csrc/hgin_linklse.hip);
 ``full_softmax_link_loss`` is the per-positive cross-entropy over it, ``LinkPredictor.full_loss`` /
 ``batch_full_loss`` train on it (the latter with a mini-batch's destination seeds as in-batch negatives);
-``link_lse_unfused`` is the kept torch baseline.
+``link_lse_unfused`` is the kept torch baseline.  With ``segments=`` (A24) all of them sum over the destinations of
+the source's own graph only, and sweep only the tiles those graphs cover.
 """
 from __future__ import annotations
 
@@ -964,18 +965,24 @@ def _lse_operands(what: str, z_src: Tensor, z_dst: Tensor, src: Tensor, temperat
 
 class _LinkLseFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, z_src, z_dst, src, inv_t: float, rowptr, col):
+    def forward(ctx, z_src, z_dst, src, inv_t: float, rowptr, col, segments=None):
         dev = z_src.device
         Q, n_src, n_dst, F = int(src.numel()), int(z_src.size(0)), int(z_dst.size(0)), int(z_src.size(1))
         nbytes = ctypes.c_size_t(0)
-        _lib.check(_lib.lib().hgin_link_lse_workspace_size(Q, n_dst, F, ctypes.byref(nbytes)),
-                   "hgin_link_lse_workspace_size")
+        size = "hgin_link_lse_workspace_size" if segments is None else "hgin_link_lse_seg_workspace_size"
+        _lib.check(getattr(_lib.lib(), size)(Q, n_dst, F, ctypes.byref(nbytes)), size)
         ws = ops._workspace(nbytes.value, dev)
         lse = torch.empty(Q, dtype=torch.float32, device=dev)
-        _lib.call("hgin_link_lse_fwd_f32", ops._p(src), Q, n_src, n_dst, ops._p(z_src), z_src.stride(0), ops._p(z_dst),
-                  z_dst.stride(0), F, inv_t, ops._p(rowptr), ops._p(col), ops._p(lse), ops._p(ws), nbytes.value,
-                  ops._stream(lse))
-        ctx.inv_t, ctx.ws_bytes, ctx.known = inv_t, nbytes.value, (rowptr, col)
+        if segments is None:
+            _lib.call("hgin_link_lse_fwd_f32", ops._p(src), Q, n_src, n_dst, ops._p(z_src), z_src.stride(0),
+                      ops._p(z_dst), z_dst.stride(0), F, inv_t, ops._p(rowptr), ops._p(col), ops._p(lse), ops._p(ws),
+                      nbytes.value, ops._stream(lse))
+        else:
+            _lib.call("hgin_link_lse_fwd_seg_f32", ops._p(src), Q, n_src, n_dst, ops._p(z_src), z_src.stride(0),
+                      ops._p(z_dst), z_dst.stride(0), F, inv_t, ops._p(rowptr), ops._p(col), ops._p(lse), ops._p(ws),
+                      nbytes.value, ops._p(segments.src_seg), ops._p(segments.dst_ptr), segments.n_graphs,
+                      ops._stream(lse))
+        ctx.inv_t, ctx.ws_bytes, ctx.known, ctx.segments = inv_t, nbytes.value, (rowptr, col), segments
         ctx.save_for_backward(z_src, z_dst, src, lse)
         return lse
 
@@ -983,47 +990,74 @@ class _LinkLseFn(torch.autograd.Function):
     def backward(ctx, g):
         z_src, z_dst, src, lse = ctx.saved_tensors
         rowptr, col = ctx.known
+        seg = ctx.segments
         g = g.to(torch.float32).contiguous()
         Q, n_src, n_dst, F = int(src.numel()), int(z_src.size(0)), int(z_dst.size(0)), int(z_src.size(1))
         g_src = g_dst = None
         ws = None       # one workspace for both kernels: they run one after the other on this stream
-        for i, name in ((0, "hgin_link_lse_bwd_src_f32"), (1, "hgin_link_lse_bwd_dst_f32")):
+        for i, side in ((0, "src"), (1, "dst")):
             if not ctx.needs_input_grad[i]:
                 continue
             out = torch.empty_like(z_src if i == 0 else z_dst, memory_format=torch.contiguous_format)
             if ws is None:
                 ws = ops._workspace(ctx.ws_bytes, z_src.device)
-            _lib.call(name, ops._p(src), Q, n_src, n_dst, ops._p(z_src), z_src.stride(0), ops._p(z_dst),
-                      z_dst.stride(0), F, ctx.inv_t, ops._p(rowptr), ops._p(col), ops._p(lse), ops._p(g), ops._p(out),
-                      out.stride(0), ops._p(ws), ctx.ws_bytes, ops._stream(out))
+            if seg is None:
+                _lib.call(f"hgin_link_lse_bwd_{side}_f32", ops._p(src), Q, n_src, n_dst, ops._p(z_src), z_src.stride(0),
+                          ops._p(z_dst), z_dst.stride(0), F, ctx.inv_t, ops._p(rowptr), ops._p(col), ops._p(lse),
+                          ops._p(g), ops._p(out), out.stride(0), ops._p(ws), ctx.ws_bytes, ops._stream(out))
+            else:
+                _lib.call(f"hgin_link_lse_bwd_{side}_seg_f32", ops._p(src), Q, n_src, n_dst, ops._p(z_src),
+                          z_src.stride(0), ops._p(z_dst), z_dst.stride(0), F, ctx.inv_t, ops._p(rowptr), ops._p(col),
+                          ops._p(lse), ops._p(g), ops._p(out), out.stride(0), ops._p(ws), ctx.ws_bytes,
+                          ops._p(seg.src_seg), ops._p(seg.dst_ptr), seg.n_graphs, ops._stream(out))
             if i == 0:
                 g_src = out
             else:
                 g_dst = out
-        return g_src, g_dst, None, None, None, None
+        return g_src, g_dst, None, None, None, None, None
 
 
-def link_lse(z_src: Tensor, z_dst: Tensor, src: Tensor, temperature: float = 1.0, known: Tensor = None) -> Tensor:
+def _lse_segments(what: str, segments, z_src, z_dst) -> None:
+    """``segments`` of ``link_lse`` / ``link_lse_unfused``: a ``LinkSegments`` that fits the embeddings' row counts and
+    lives on their device (checked before a device is needed)."""
+    _check_segments(what, segments, z_src.size(0) if isinstance(z_src, Tensor) and z_src.dim() else -1,
+                    z_dst.size(0) if isinstance(z_dst, Tensor) and z_dst.dim() else -1)
+    if isinstance(z_src, Tensor) and z_src.device != segments.device:
+        raise ValueError(f"{what}: z_src is on {z_src.device}, segments on {segments.device}")
+
+
+def link_lse(z_src: Tensor, z_dst: Tensor, src: Tensor, temperature: float = 1.0, known: Tensor = None,
+             segments: LinkSegments = None) -> Tensor:
     """float32 [Q] (include/hgin.h A23): for every source ``src[q]`` (int64 [Q], distinct: checked once per tensor
     version with one host sync, ValueError) the log-sum-exp over *every* destination c of
     <z_src[src[q]], z_dst[c]> / temperature, minus the c with (src[q], c) in ``known`` (an edge index [2, M]; None: every
     destination); -inf for a source whose destinations are all known.  The scores are the bits ``link_full_ranks`` /
     ``link_topk`` compare; no [Q, n_dst] matrix exists in the forward or in the backward (two kernels that recompute the
-    scores, csrc/hgin_linklse.hip); forward and gradients are run-to-run identical."""
+    scores, csrc/hgin_linklse.hip); forward and gradients are run-to-run identical.
+
+    With ``segments`` (a ``LinkSegments``; include/hgin.h A24) the sum runs only over the destinations of the source's
+    own graph: known neighbours outside it are irrelevant, a source whose graph has no destination gives -inf and no
+    gradient, and a block of 128 queries sweeps only the destination tiles its graphs cover, so sort ``src`` by graph
+    to visit n_dst / G instead of n_dst (any order is correct).  One graph gives the unsegmented bits."""
     what = "link_lse"
+    if segments is not None:
+        _lse_segments(what, segments, z_src, z_dst)
     z_src, z_dst, src, inv_t, rowptr, col = _lse_operands(what, z_src, z_dst, src, temperature, known)
-    return _LinkLseFn.apply(z_src, z_dst, src, inv_t, rowptr, col)
+    return _LinkLseFn.apply(z_src, z_dst, src, inv_t, rowptr, col, segments)
 
 
 LSE_UNFUSED_BYTES = 1 << 30     # fp32 scores per chunk of the unfused baseline
 
 
 def link_lse_unfused(z_src: Tensor, z_dst: Tensor, src: Tensor, temperature: float = 1.0, known: Tensor = None,
-                     chunk_rows: int = None) -> Tensor:
+                     chunk_rows: int = None, segments: LinkSegments = None) -> Tensor:
     """``link_lse`` as plain torch, the kept baseline the fused path is checked and timed against: chunks of query rows
     (about 1 GB of fp32 scores each, or ``chunk_rows``) of ``z_src[src] @ z_dst.T * fl32(1 / temperature)``, known edges
-    set to -inf, ``torch.logsumexp``.  It materialises a chunk of the [Q, n_dst] matrix, and autograd keeps it."""
+    (and, with ``segments``, the columns outside the source's own graph) set to -inf, ``torch.logsumexp``.  It
+    materialises a chunk of the [Q, n_dst] matrix, and autograd keeps it."""
     what = "link_lse_unfused"
+    if segments is not None:
+        _lse_segments(what, segments, z_src, z_dst)
     z_src, z_dst, src, inv_t, rowptr, col = _lse_operands(what, z_src, z_dst, src, temperature, known)
     Q, n_dst = int(src.numel()), int(z_dst.size(0))
     rows = int(chunk_rows) if chunk_rows else max(1, LSE_UNFUSED_BYTES // (4 * n_dst))
@@ -1040,6 +1074,12 @@ def link_lse_unfused(z_src: Tensor, z_dst: Tensor, src: Tensor, temperature: flo
             mask = torch.zeros_like(t, dtype=torch.bool)
             mask[qi, ci] = True
             t = t.masked_fill(mask, float("-inf"))
+        if segments is not None:
+            gph = segments.src_seg[s].long()
+            ptr = segments.dst_ptr.long()
+            c = torch.arange(n_dst, device=s.device)
+            outside = (c[None, :] < ptr[gph][:, None]) | (c[None, :] >= ptr[gph + 1][:, None])
+            t = t.masked_fill(outside, float("-inf"))
         out.append(torch.logsumexp(t, 1))
     return torch.cat(out)
 
@@ -1069,7 +1109,7 @@ def _full_softmax_plan(pos: Tensor, known: Optional[Tensor], n_src: int, n_dst: 
 
 
 def full_softmax_link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, temperature: float = 1.0,
-                           known: Tensor = None) -> Tensor:
+                           known: Tensor = None, segments: LinkSegments = None) -> Tensor:
     """Softmax cross-entropy of every positive (s, d) of ``pos`` (int64 [2, E]) against *every* destination (a scalar):
     mean over the positives of log sum_c exp(score(s, c) / T) - score(s, d) / T, on ``link_lse`` (one query per distinct
     source) and ``dot_decode``.  ``known`` = None: the sum runs over every destination,
@@ -1077,8 +1117,13 @@ def full_softmax_link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, temperatur
     the denominator while the positive stays in its own: lse_neg = ``link_lse`` filtered by ``known`` and ``pos``
     together, loss = mean_e softplus(lse_neg[s_e] - s_e).  Deterministic forward and backward: the per-positive read of
     lse_neg is a ``dot_decode`` of a one-column embedding against a column of ones, whose backward is the store-and-sum
-    over the static CSC of ``pos``."""
+    over the static CSC of ``pos``.  With ``segments`` (a ``LinkSegments``; include/hgin.h A24) "every destination" is
+    every destination of the positive's own graph, the denominator ``link_full_metrics(segments=)`` ranks against; a
+    positive whose destination lies outside its source's graph is refused (ValueError)."""
     what = "full_softmax_link_loss"
+    if segments is not None:
+        _check_segments(what, segments, z_src.size(0) if z_src.dim() else -1, z_dst.size(0) if z_dst.dim() else -1,
+                        pos if isinstance(pos, Tensor) and pos.dim() == 2 and pos.dtype == torch.long else None)
     for name, z in (("z_src", z_src), ("z_dst", z_dst)):
         if z.dtype != torch.float32:
             raise TypeError(f"{what}: {name} must be float32 (the fused link kernels are fp32 only), got {z.dtype}")
@@ -1096,9 +1141,9 @@ def full_softmax_link_loss(z_src: Tensor, z_dst: Tensor, pos: Tensor, temperatur
     s_e = dot_decode(z_src, z_dst, pos) * ctypes.c_float(1.0 / temperature).value   # range-checks pos (relation_graph)
     u, cnt, both = _full_softmax_plan(pos, known, n_src, n_dst)
     if known is None:
-        lse = link_lse(z_src, z_dst, u, temperature)
+        lse = link_lse(z_src, z_dst, u, temperature, segments=segments)
         return ((cnt * lse).sum() - s_e.sum()) / E
-    lse_neg = link_lse(z_src, z_dst, u, temperature, known=both)
+    lse_neg = link_lse(z_src, z_dst, u, temperature, known=both, segments=segments)
     col = torch.zeros(n_src, dtype=torch.float32, device=z_src.device).index_copy(0, u, lse_neg)
     ones = torch.ones(n_dst, 1, dtype=torch.float32, device=z_src.device)
     lse_e = dot_decode(col.unsqueeze(1), ones, pos)     # lse_neg of every positive's source: x * 1.0 is exact
@@ -1315,14 +1360,23 @@ class LinkPredictor:
         if self.hard > 0 or self.graph_local:
             raise ValueError(f"{what}: hard > 0 and graph_local = True are not supported by the full softmax loss")
 
-    def full_loss(self, graph, pos: Tensor = None, known: Tensor = None) -> Tensor:
+    def full_loss(self, graph, pos: Tensor = None, known: Tensor = None, segments: LinkSegments = None) -> Tensor:
         """``full_softmax_link_loss`` of ``pos`` (default: the relation's own edges) at the predictor's ``temperature``:
         every positive against every destination of the graph (include/hgin.h A23); k, seed and the objective play no
         part.  ``known`` (an edge index; default with ``filter_negatives``: the relation's own edges) takes a source's
-        other true edges out of the denominator.  ``hard`` > 0 and ``graph_local`` are not supported (ValueError)."""
+        other true edges out of the denominator.  On a collated batch of graphs pass
+        ``segments=LinkSegments.of(graph, relation)`` (include/hgin.h A24): every positive then stands against the
+        destinations of its own graph only, the denominator ``full_metrics`` of a ``graph_local`` predictor ranks
+        against.  ``segments=`` is the way in: ``hard`` > 0 and a predictor built with ``graph_local`` are still refused
+        (ValueError)."""
         self._no_full("LinkPredictor.full_loss")
+        if segments is not None and not isinstance(segments, LinkSegments):
+            raise TypeError(f"LinkPredictor.full_loss: segments must be a LinkSegments, got {type(segments).__name__}")
         pos = self._pos(graph, pos)
         z = self.model.encode(graph.x_dict(), graph.edge_index_dict())
+        if segments is not None:
+            return full_softmax_link_loss(z[self.relation[0]], z[self.relation[2]], pos, self.temperature,
+                                          segments=segments, **self._known_kw(graph, known))
         return full_softmax_link_loss(z[self.relation[0]], z[self.relation[2]], pos, self.temperature,
                                       **self._known_kw(graph, known))
 

@@ -857,6 +857,48 @@ int hgin_link_lse_bwd_dst_f32(const int64_t* src, int64_t n_query, int64_t n_src
                               const int32_t* known_rowptr, const int32_t* known_col, const float* lse, const float* g,
                               float* g_dst, int64_t ld_gdst, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- A24: graph-local candidates for the full softmax link loss (NOT IN REFERENCE; build-defined; added to ABI 16
+ * without a bump: purely additive, no earlier entry point changes) -----------------------------------------------------
+ * A23 over A19's segmentation (src_seg int32 [n_src], dst_ptr int32 [n_graphs + 1]).  For s = src[q], [lo, lo + n) is
+ * A19's segment of s (g = src_seg[s] clamped into [0, n_graphs), dst_ptr values kept inside [0, n_dst]):
+ *   cand(q) = { c in [lo, lo + n) : (s, c) not in known }
+ * and t, lse, P, g_src, g_dst are A23's over these candidates.  Known neighbours outside the segment are irrelevant.
+ * lse[q] = -inf when n = 0 or the whole segment is known; both gradients are then exact zeros.  Scores keep the A15 K
+ * order: a (query row, destination row) pair carries the bits it carries unsegmented, wherever its tile lies, and with
+ * n_graphs = 1 all three calls give the unsegmented calls' bits (the slice rule below then cuts A23's splits).  The
+ * unsegmented entry points, their launches and their bits are unchanged; the segmented kernels are separate
+ * instantiations (traced as k_lse_sweep<4,SEG> / k_lse_bwd<4,SRC,SEG> / k_lse_bwd<4,DST,SEG>).
+ *   hgin_link_lse_fwd_seg_f32, hgin_link_lse_bwd_src_seg_f32 (query-stationary): a lane keeps lo and n per query column
+ *     and counts a destination only inside them; a workgroup sweeps only the tiles min lo / 128 .. ceil(max hi / 128)
+ *     of its 128 queries (A19's block-wide min / max); split i of A23's `splits` takes the i-th slice of
+ *     ceil(tiles / splits) of that range.  A slice may be empty: it then contributes (-inf, 0) to the merge and zeros
+ *     to the fold.  Queries sorted by graph cost n_query n_dst / G instead of n_query n_dst.
+ *   hgin_link_lse_bwd_dst_seg_f32 (tile-stationary): a small pre-kernel writes every query block's covered range
+ *     [min lo, max hi) into the workspace; a workgroup skips, whole (no loads, no matrix-core work), every query block
+ *     of its sweep whose range misses its tile, and prefetches the next block that is not skipped.  A tile every block
+ *     skips writes zeros (g_dst need not be cleared by the caller).  Queries in any order are correct; shuffled ones
+ *     skip nothing.
+ * Deterministic as A23.  Workspace: hgin_link_lse_seg_workspace_size (>= A23's: 8 bytes per query block more behind
+ * the g_dst partials) covers all three calls.  Status as A23, plus HGIN_E_ARG before any launch for src_seg or dst_ptr =
+ * NULL or n_graphs outside [1, 2^31).  The caller guarantees 0 <= src_seg < n_graphs and a valid dst_ptr; nothing is read
+ * out of range even so. */
+int hgin_link_lse_seg_workspace_size(int64_t n_query, int64_t n_dst, int64_t F, size_t* bytes);
+int hgin_link_lse_fwd_seg_f32(const int64_t* src, int64_t n_query, int64_t n_src, int64_t n_dst, const float* z_src,
+                              int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F, float inv_t,
+                              const int32_t* known_rowptr, const int32_t* known_col, float* lse, void* ws,
+                              size_t ws_bytes, const int32_t* src_seg, const int32_t* dst_ptr, int64_t n_graphs,
+                              void* stream);
+int hgin_link_lse_bwd_src_seg_f32(const int64_t* src, int64_t n_query, int64_t n_src, int64_t n_dst,
+                                  const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F,
+                                  float inv_t, const int32_t* known_rowptr, const int32_t* known_col, const float* lse,
+                                  const float* g, float* g_src, int64_t ld_gsrc, void* ws, size_t ws_bytes,
+                                  const int32_t* src_seg, const int32_t* dst_ptr, int64_t n_graphs, void* stream);
+int hgin_link_lse_bwd_dst_seg_f32(const int64_t* src, int64_t n_query, int64_t n_src, int64_t n_dst,
+                                  const float* z_src, int64_t ld_src, const float* z_dst, int64_t ld_dst, int64_t F,
+                                  float inv_t, const int32_t* known_rowptr, const int32_t* known_col, const float* lse,
+                                  const float* g, float* g_dst, int64_t ld_gdst, void* ws, size_t ws_bytes,
+                                  const int32_t* src_seg, const int32_t* dst_ptr, int64_t n_graphs, void* stream);
+
 /* ---- F4 widening: HetroGAT's graph attention (models.py:380-506, PyG 2.0.2 GATConv) ---------------------------
  * x_s / x_d: projected source / destination features [N, H * C] (row stride ld*), edges = the relation after
  * GATConv's self-loop handling, as CSR by destination (rowptr, col) and CSC by source (cptr, cdst, cpos = the CSR

@@ -14,10 +14,16 @@ peak come from a separate ``rocprofv3 --kernel-trace --stats`` run of this tool 
 ``--rates-from`` then reduces (median duration of each A23 kernel, divided into ``kernel_flop``; needs no device).
 There is no CPU fallback: without a HIP device the tool prints the plan and fails.
 
+``--graphs G`` (A24) cuts every shape into G equal graphs (sources, queries and destinations; the remainders are
+dropped) and times ``link_lse(segments=)`` forward + backward against the same call without ``segments`` and against
+``link_lse_unfused(segments=)``: the same tensors, the three paths alternating in one run, once with the queries sorted
+by graph and once shuffled; known edges (where the shape has them) stay inside the source's graph.
+
     python tools/bench_linklse.py --out profiles/linklse/linklse_bench.json
     python tools/bench_linklse.py --scale 0.01 --queries 256          # a tiny run
     rocprofv3 --kernel-trace --stats -d prof -o cfg2 --output-format csv -- python tools/bench_linklse.py --only cfg2
     python tools/bench_linklse.py --only cfg2 --rates-from prof/cfg2_kernel_trace.csv --out rates_cfg2.json
+    python tools/bench_linklse.py --graphs 8 --only inbatch_f128,cfg2 --out profiles/linklse/linklse_seg_bench.json
 """
 import argparse
 import importlib.util
@@ -104,6 +110,88 @@ def plan(scale: float = 1.0, queries: int = 4096):
     return shapes
 
 
+def seg_plan(shape: dict, graphs: int) -> dict:
+    """``shape`` cut into ``graphs`` equal graphs: every count rounded down to a multiple of G; ``flop`` is the
+    unsegmented work of the cut shape, ``flop_seg`` the work the candidates need (1 / G of it)."""
+    G = int(graphs)
+    if G < 1 or G > min(shape["Q"], shape["n_src"], shape["n_dst"]):
+        raise ValueError(f"--graphs must be in [1, min(Q, n_src, n_dst)], got {G}")
+    out = dict(shape, graphs=G)
+    for k in ("Q", "n_src", "n_dst"):
+        out[k] = shape[k] - shape[k] % G
+    out["queries_per_graph"], out["dst_per_graph"] = out["Q"] // G, out["n_dst"] // G
+    out["flop"] = kernel_flop(out["Q"], out["n_dst"], out["F"])
+    out["flop_seg"] = {k: v // G for k, v in out["flop"].items()}
+    out["score_bytes_not_materialised"] = 4 * out["Q"] * out["n_dst"]
+    out["baseline_chunk_rows"] = max(1, CHUNK_BYTES // (4 * out["n_dst"]))
+    return out
+
+
+def run_seg_shape(torch, shape, repeats, warmup, target_ms, seed=1234):
+    """``shape`` = a ``seg_plan``.  Per query order (sorted by graph, shuffled): the three paths' windows, segmented over
+    unsegmented, and whether the difference is beyond the spread."""
+    lp = _tool("bench_linkpred")
+    from hgin.linkpred import LinkSegments, link_lse, link_lse_unfused
+    dev = "cuda"
+    n_src, n_dst, F, Q, deg, G = (shape[x] for x in ("n_src", "n_dst", "F", "Q", "known_degree", "graphs"))
+    g = torch.Generator(device=dev).manual_seed(seed)
+    z_src = (torch.randn(n_src, F, generator=g, device=dev) * 0.1).requires_grad_(True)
+    z_dst = (torch.randn(n_dst, F, generator=g, device=dev) * 0.1).requires_grad_(True)
+    per_src, per_dst = n_src // G, n_dst // G
+    batch_src = torch.arange(n_src, device=dev) // per_src
+    segments = LinkSegments(batch_src, torch.arange(n_dst, device=dev) // per_dst, G)
+    shuffled = torch.randperm(n_src, generator=g, device=dev)[:Q].contiguous()
+    orders = {"sorted": shuffled[torch.sort(batch_src[shuffled], stable=True).indices].contiguous(),
+              "shuffled": shuffled}
+    chunk = shape["baseline_chunk_rows"]
+    out = dict(shape)
+    for order, src in orders.items():
+        known = None
+        if deg:
+            s_rep = src.repeat_interleave(deg)
+            inside = torch.randint(0, per_dst, (Q * deg,), generator=g, device=dev)
+            known = torch.stack([s_rep, batch_src[s_rep] * per_dst + inside])
+
+        def step_of(fn, **kw):
+            def step(_):
+                z_src.grad = z_dst.grad = None
+                lse = fn(z_src, z_dst, src, 0.5, known, **kw)
+                lse.sum().backward()
+                return lse
+            return step
+
+        paths = {"seg": step_of(link_lse, segments=segments), "unseg": step_of(link_lse),
+                 "unfused_seg": step_of(link_lse_unfused, chunk_rows=chunk, segments=segments)}
+        res, grads = {}, {}
+        for _ in range(warmup):
+            for name, fn in paths.items():
+                res[name] = fn(0).detach()
+                grads[name] = (z_src.grad.clone(), z_dst.grad.clone())
+        torch.cuda.synchronize()
+        o = {"max_abs_lse_difference": float((res["seg"] - res["unfused_seg"]).abs().max()),
+             "max_abs_grad_difference": max(float((a - b).abs().max())
+                                            for a, b in zip(grads["seg"], grads["unfused_seg"]))}
+        res.clear()
+        grads.clear()
+        inner = {name: lp._inner_for(torch, fn, target_ms) for name, fn in paths.items()}
+        times = {name: [] for name in paths}
+        for _ in range(repeats):      # the paths alternate
+            for name, fn in paths.items():
+                times[name].append(lp._timed(torch, fn, inner[name], 0))
+        for name in paths:
+            o[name] = dict(lp._stats(times[name]), inner=inner[name])
+            print(f"{shape['name']} known={deg} G={G} {order}: {name}: median {o[name]['median_ms']:.3f} ms "
+                  f"[{o[name]['min_ms']:.3f} - {o[name]['max_ms']:.3f}]", file=sys.stderr, flush=True)
+        o["seg_over_unseg"] = o["seg"]["median_ms"] / o["unseg"]["median_ms"]
+        o["seg_faster_beyond_spread"] = o["seg"]["max_ms"] < o["unseg"]["min_ms"]
+        o["seg_slower_beyond_spread"] = o["seg"]["min_ms"] > o["unseg"]["max_ms"]
+        o["unfused_seg_over_seg"] = o["unfused_seg"]["median_ms"] / o["seg"]["median_ms"]
+        out[order] = o
+    del z_src, z_dst
+    torch.cuda.empty_cache()
+    return out
+
+
 def run_shape(torch, shape, repeats, warmup, target_ms, seed=1234):
     lp = _tool("bench_linkpred")
     from hgin.linkpred import link_lse, link_lse_unfused
@@ -165,6 +253,9 @@ def main(argv=None) -> int:
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--target-ms", type=float, default=30.0, help="device time of one timed window, at least")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--graphs", type=int, default=0, metavar="G",
+                    help="cut every shape into G equal graphs and time link_lse(segments=) against the unsegmented call "
+                         "and link_lse_unfused(segments=), queries sorted by graph and shuffled")
     ap.add_argument("--rates-from", default=None, metavar="TRACE.csv",
                     help="reduce the rocprofv3 kernel trace of a run on the one shape named by --only; no device needed")
     args = ap.parse_args(argv)
@@ -172,9 +263,16 @@ def main(argv=None) -> int:
         ap.error("--repeats must be at least 5")
     if args.queries < 1 or args.warmup < 1:
         ap.error("--queries and --warmup must be at least 1")
+    if args.graphs < 0 or (args.graphs and args.rates_from):
+        ap.error("--graphs must be positive and does not combine with --rates-from")
     shapes = plan(args.scale, args.queries)
     if args.only:
         shapes = [s for s in shapes if s["name"] in args.only.split(",")]
+    if args.graphs:
+        try:
+            shapes = [seg_plan(s, args.graphs) for s in shapes]
+        except ValueError as e:
+            ap.error(str(e))
     for s in shapes:
         print("plan:", json.dumps(s), file=sys.stderr)
     if args.rates_from:
@@ -196,11 +294,16 @@ def main(argv=None) -> int:
         return 2
     from hgin import _lib
     _lib.lib()
-    results = [run_shape(torch, s, args.repeats, args.warmup, args.target_ms) for s in shapes]
-    doc = {"tool": "tools/bench_linklse.py", "device": torch.cuda.get_device_name(0),
-           "f32_mfma_peak_flop_per_s": F32_MFMA_PEAK, "arithmetic": "v_mfma_f32_32x32x2_f32",
-           "repeats": args.repeats, "warmup": args.warmup, "shapes": results,
-           "fused_faster_at_every_shape": all(r["fused_faster_beyond_spread"] for r in results)}
+    if args.graphs:
+        results = [run_seg_shape(torch, s, args.repeats, args.warmup, args.target_ms) for s in shapes]
+        doc = {"tool": f"tools/bench_linklse.py --graphs {args.graphs}", "device": torch.cuda.get_device_name(0),
+               "graphs": args.graphs, "repeats": args.repeats, "warmup": args.warmup, "shapes": results}
+    else:
+        results = [run_shape(torch, s, args.repeats, args.warmup, args.target_ms) for s in shapes]
+        doc = {"tool": "tools/bench_linklse.py", "device": torch.cuda.get_device_name(0),
+               "f32_mfma_peak_flop_per_s": F32_MFMA_PEAK, "arithmetic": "v_mfma_f32_32x32x2_f32",
+               "repeats": args.repeats, "warmup": args.warmup, "shapes": results,
+               "fused_faster_at_every_shape": all(r["fused_faster_beyond_spread"] for r in results)}
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
