@@ -209,6 +209,9 @@ _SIGS = {
     "hgin_neighbor_sample_offsets": ([_P, _I64, _P, _I64, _I32, _P, _P, _SZ, _P], _I32),
     "hgin_neighbor_sample": ([_P, _P, _P, _I64, _P, _I64, _I32, _U64, ctypes.c_uint32, _I64, _P, _P, _P, _I64, _P],
                              _I32),
+    "hgin_neighbor_sample_offsets_excl": ([_P, _P, _I64, _P, _I64, _I32, _P, _I64, _P, _P, _SZ, _P], _I32),
+    "hgin_neighbor_sample_excl": ([_P, _P, _P, _I64, _P, _I64, _I32, _U64, ctypes.c_uint32, _I64, _P, _I64, _P, _P, _P,
+                                   _I64, _P], _I32),
     "hgin_neighbor_fresh": ([_P, _I64, _P, _I64, _I64, _P, _P], _I32),
     "hgin_neighbor_map_set": ([_P, _I64, _P, _I64, _I64, _P], _I32),
     "hgin_neighbor_emit": ([_P, _I64, _P, _P, _I64, _I64, _I64, _P, _P], _I32),

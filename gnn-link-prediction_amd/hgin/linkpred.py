@@ -44,7 +44,8 @@ source whose window is all neighbours keeps the unfiltered draw; given negatives
 Mini-batches (A22, not in the reference): ``link_neighbor_batch`` seeds a ``hgin.neighbor.NeighborSampler`` with a batch's
 positives (and given negatives) and returns them as local rows of the sampled subgraph; ``LinkPredictor.batch_loss``
 draws the negatives ``loss`` would draw, encodes that subgraph only and scores on the fused loss
-(hgin/train.py::link_minibatch_step).
+(hgin/train.py::link_minibatch_step).  ``link_neighbor_batch_excl`` / ``LinkPredictor(exclude_targets=True)`` (A25) keep
+the batch's own positives, and their flips in the reverse relation, out of the neighbourhood that batch is encoded on.
 
 Full softmax (A23, not in the reference): ``link_lse`` is the log-sum-exp of a source's scores over *every* destination
 (known edges masked), forward and backward on the matrix cores without a score matrix (csrc/hgin_linklse.hip);
@@ -1168,11 +1169,17 @@ class LinkPredictor:
     ``filter_negatives`` = True draws the uniform negatives of ``loss`` and ``metrics`` from each source's
     non-neighbours (include/hgin.h A20): ``known`` = the relation's edges in the graph, or what the call's own
     ``known=`` gives (train + valid + test edges for held-out positives).  It composes with ``graph_local``, ``hard``
-    (whose mined set is filtered by the relation's edges already; its padding fill is not) and every objective."""
+    (whose mined set is filtered by the relation's edges already; its padding fill is not) and every objective.
+
+    ``exclude_targets`` = True makes ``batch_loss`` and ``batch_full_loss`` build their mini-batch with
+    ``link_neighbor_batch_excl`` (include/hgin.h A25): the batch's positives, and their flips in ``rev_relation``
+    (``"auto"``, None or a relation, resolved against the sampler's graph as ``link_split`` resolves it), are not edges
+    of the neighbourhood that batch is encoded on.  Drawn or given negatives are seeds, never excluded pairs.  The
+    default leaves every output as it was."""
 
     def __init__(self, model, relation, k: int, seed: int, objective: str = "bce", temperature: float = 1.0,
                  alpha: float = 1.0, hard: int = 0, mine_every: int = 1, graph_local: bool = False,
-                 filter_negatives: bool = False):
+                 filter_negatives: bool = False, exclude_targets: bool = False, rev_relation="auto"):
         if not hasattr(model, "encode"):
             raise TypeError("LinkPredictor: the model has no encode(x_dict, edge_index_dict)")
         _objective("LinkPredictor", objective, temperature, alpha)
@@ -1191,6 +1198,16 @@ class LinkPredictor:
         self.graph_local = bool(graph_local)
         self._segments = None     # (graph, its LinkSegments) of the last graph seen with graph_local
         self.filter_negatives = bool(filter_negatives)
+        self.exclude_targets = bool(exclude_targets)
+        self.rev_relation = rev_relation
+
+    def _batch(self, sampler, pos, neg, step) -> "LinkBatch":
+        """The mini-batch of ``batch_loss`` / ``batch_full_loss``: ``link_neighbor_batch``, or with ``exclude_targets``
+        ``link_neighbor_batch_excl`` (the positives and their flips leave the batch's own neighbourhood)."""
+        if self.exclude_targets:
+            return link_neighbor_batch_excl(sampler, self.relation, pos, neg, offset=int(step),
+                                            rev_relation=self.rev_relation)
+        return link_neighbor_batch(sampler, self.relation, pos, neg, offset=int(step))
 
     def _seg_kw(self, graph) -> dict:
         """{} by default (every call below is then exactly the unsegmented one), {"segments": ...} with graph_local."""
@@ -1350,7 +1367,7 @@ class LinkPredictor:
             csr = _known_csr(known, sampler.num_nodes[self.relation[0]], n_dst)
             neg = _sample_filt(pos[0], self.k, self.seed, draw_at, n_dst, None, csr)
         neg = neg.view(B, self.k)
-        batch = link_neighbor_batch(sampler, self.relation, pos, neg, offset=int(step))
+        batch = self._batch(sampler, pos, neg, step)
         g = batch.sub.graph
         z = self.model.encode(g.x_dict(), g.edge_index_dict())
         return sampled_link_loss(z[self.relation[0]], z[self.relation[2]], batch.pos, 0, self.seed, 0, self.objective,
@@ -1408,7 +1425,7 @@ class LinkPredictor:
             _known_shape(what, known)
         ops.require_device(pos, known, what=what)
         s_type, d_type = self.relation[0], self.relation[2]
-        batch = link_neighbor_batch(sampler, self.relation, pos, None, offset=int(step))
+        batch = self._batch(sampler, pos, None, step)
         g = batch.sub.graph
         z = self.model.encode(g.x_dict(), g.edge_index_dict())
         local_known = batch.pos
@@ -1441,15 +1458,54 @@ def link_neighbor_batch(sampler, relation, pos: Tensor, neg_dst: Tensor = None, 
         raise TypeError(f"{what}: pos must be an int64 edge index [2, B], got {got}")
     if pos.dim() != 2 or int(pos.size(0)) != 2:
         raise ValueError(f"{what}: pos must be [2, B], got {tuple(pos.shape)}")
+    return _link_batch(what, sampler, relation, pos, neg_dst, offset, None)
+
+
+def _link_batch(what, sampler, relation, pos, neg_dst, offset, exclude) -> LinkBatch:
+    """``link_neighbor_batch``'s body; ``exclude`` = None samples with ``sampler.sample``, a dict with
+    ``sampler.sample_excluding``."""
     m = _given_shape(what, neg_dst, pos)
     s_type, d_type = relation[0], relation[2]
     dst = pos[1] if m == 0 else torch.cat([pos[1], neg_dst.reshape(-1).long()])
     seeds = {s_type: torch.cat([pos[0], dst])} if s_type == d_type else {s_type: pos[0], d_type: dst}
-    sub = sampler.sample(seeds, offset=offset)
+    if exclude is None:
+        sub = sampler.sample(seeds, offset=offset)
+    else:
+        sub = sampler.sample_excluding(seeds, exclude, offset=offset)
     local = torch.stack([sub._rows(s_type, pos[0]), sub._rows(d_type, pos[1])])
     neg_local = None
     if m:
         neg_local = sub._rows(d_type, neg_dst.long().contiguous()).to(torch.int32)
         _mark_checked(neg_local, int(sub.n_id[d_type].numel()))
     return LinkBatch(sub, local, neg_local)
+
+
+def link_neighbor_batch_excl(sampler, relation, pos: Tensor, neg_dst: Tensor = None, offset: int = 0,
+                             rev_relation="auto") -> LinkBatch:
+    """``link_neighbor_batch`` without the batch's own target edges (include/hgin.h A25): the seeds are the same, and
+    the subgraph comes from ``sampler.sample_excluding`` with the pairs ``pos`` in ``relation`` and their flips
+    ``pos.flip(0)`` in ``rev_relation``, each only where the sampler convolves over that relation.  ``rev_relation`` is
+    resolved against ``sampler.graph`` as ``link_split`` resolves it: ``"auto"`` = the one relation (dst_type, *,
+    src_type), none when there is no such relation, ValueError when there are several; None = none; or a relation.
+    The negatives ``neg_dst`` are seeds, never excluded pairs."""
+    from .linksplit import _reverse_of
+    from .neighbor import NeighborSampler
+    what = "link_neighbor_batch_excl"
+    if not isinstance(sampler, NeighborSampler):
+        raise TypeError(f"{what}: sampler must be a NeighborSampler, got {type(sampler).__name__}")
+    relation = tuple(relation)
+    if len(relation) != 3:
+        raise ValueError(f"{what}: relation must be (src_type, name, dst_type), got {relation!r}")
+    if not isinstance(pos, Tensor) or pos.dtype != torch.long:
+        got = pos.dtype if isinstance(pos, Tensor) else type(pos).__name__
+        raise TypeError(f"{what}: pos must be an int64 edge index [2, B], got {got}")
+    if pos.dim() != 2 or int(pos.size(0)) != 2:
+        raise ValueError(f"{what}: pos must be [2, B], got {tuple(pos.shape)}")
+    rev = _reverse_of(what, sampler.graph, relation, rev_relation)
+    exclude = {}
+    if relation in sampler.relations:
+        exclude[relation] = pos
+    if rev is not None and rev in sampler.relations:
+        exclude[rev] = pos.flip(0)
+    return _link_batch(what, sampler, relation, pos, neg_dst, offset, exclude)
 

@@ -13,8 +13,17 @@ and the relabelled edge lists are HIP kernels (csrc/hgin_neighbor.hip); ``unique
 ``x[n_id]`` and the host reads of sizes are torch.  A batch costs one host read for the seed range check, one per hop for
 the hop's edge counts, and the size read inside every ``torch.unique`` (one per type for the seeds and per hop).
 
-Messages flow over whatever is in the sampler's graph: the supervised positives of a batch should not be edges of it
-(``hgin.link_split(..., disjoint=...)`` sets such positives aside).
+Messages flow over whatever is in the sampler's graph.  Where the supervised positives of a batch are edges of it,
+``sample_excluding`` (include/hgin.h A25) leaves them out of that batch's neighbourhood, at every hop and in every
+relation that is given pairs (``hgin.link_neighbor_batch_excl`` passes the positives and their flips in the reverse
+relation; ``LinkPredictor(exclude_targets=True)`` does so for every training batch):
+
+    sub = sampler.sample_excluding(seeds, {REL_PL: pos, REL_LP: pos.flip(0)}, offset=step)
+
+The pairs become sorted keys dst * 2^32 + src (one ``torch.sort`` per relation and batch); the pick kernels drop a row's
+excluded positions and draw the fanout from what is left, so the graph and its CSRs are never rebuilt.  The alternative
+that needs no per-batch work is ``hgin.link_split(..., disjoint=...)``, which sets a fixed share of the training edges
+aside as supervision-only positives for the whole run.
 """
 from __future__ import annotations
 
@@ -151,8 +160,7 @@ class NeighborSampler:
         self._maps: Dict[str, Tensor] = {}
 
     # -------------------------------------------------------------------------------------------------
-    def _check_seeds(self, seeds, offset) -> Dict[str, Tensor]:
-        what = "NeighborSampler.sample"
+    def _check_seeds(self, seeds, offset, exclude=None, what="NeighborSampler.sample") -> Dict[str, Tensor]:
         if not isinstance(seeds, dict):
             raise TypeError(f"{what}: seeds must be a dict {{type: int64 ids}}, got {type(seeds).__name__}")
         if isinstance(offset, bool) or not isinstance(offset, numbers.Integral):
@@ -170,15 +178,37 @@ class NeighborSampler:
                 raise ValueError(f"{what}: seeds of {t!r} must be one-dimensional, got {tuple(ids.shape)}")
             if ids.numel():
                 out[t] = ids
-        devs = {v.device for v in out.values()}
+        ranged = [(f"a {t!r} seed", ids, self.num_nodes[t]) for t, ids in out.items()]
+        for r, e in (exclude or {}).items():   # the excluded pairs' ids join the one host read
+            ranged += [(f"an excluded {r[0]!r} source of {r!r}", e[0], self.num_nodes[r[0]]),
+                       (f"an excluded {r[2]!r} destination of {r!r}", e[1], self.num_nodes[r[2]])]
+        devs = {v.device for _, v, _ in ranged}
         if len(devs) > 1:
-            raise ValueError(f"{what}: seeds live on several devices {sorted(map(str, devs))}")
-        if out:   # the one host read of the check
-            ts = list(out)
-            lo_hi = torch.stack([torch.stack([out[t].amin(), out[t].amax()]) for t in ts]).tolist()
-            for t, (lo, hi) in zip(ts, lo_hi):
-                if lo < 0 or hi >= self.num_nodes[t]:
-                    raise IndexError(f"{what}: a {t!r} seed is out of range [0, {self.num_nodes[t]})")
+            raise ValueError(f"{what}: seeds{' and excluded pairs' if exclude else ''} live on several devices "
+                             f"{sorted(map(str, devs))}")
+        if ranged:   # the one host read of the check
+            lo_hi = torch.stack([torch.stack([v.amin(), v.amax()]) for _, v, _ in ranged]).tolist()
+            for (name, _, n), (lo, hi) in zip(ranged, lo_hi):
+                if lo < 0 or hi >= n:
+                    raise IndexError(f"{what}: {name} is out of range [0, {n})")
+        return out
+
+    def _check_exclude(self, exclude, what) -> Dict[tuple, Tensor]:
+        """{relation: int64 [2, M]} with M > 0 of ``exclude``, types and shapes checked (no value is read)."""
+        if not isinstance(exclude, dict):
+            raise TypeError(f"{what}: exclude must be a dict {{relation: int64 [2, M] pairs}}, got "
+                            f"{type(exclude).__name__}")
+        out = {}
+        for r, e in exclude.items():
+            if not isinstance(r, tuple) or r not in self.relations:
+                raise ValueError(f"{what}: {r!r} is not a relation of this sampler")
+            if not isinstance(e, Tensor) or e.dtype != torch.int64:
+                got = e.dtype if isinstance(e, Tensor) else type(e).__name__
+                raise TypeError(f"{what}: the excluded pairs of {r!r} must be an int64 tensor, got {got}")
+            if e.dim() != 2 or int(e.size(0)) != 2:
+                raise ValueError(f"{what}: the excluded pairs of {r!r} must be [2, M], got {tuple(e.shape)}")
+            if e.size(1):
+                out[r] = e
         return out
 
     def _device(self):
@@ -200,16 +230,34 @@ class NeighborSampler:
     def sample(self, seeds: Dict[str, Tensor], offset: int = 0) -> "SampledSubgraph":
         """The subgraph of include/hgin.h A22 around ``seeds`` = {type: int64 global ids} (repeats allowed, a type may
         be absent), for batch number ``offset`` (the second Philox counter word)."""
+        return self._sample("NeighborSampler.sample", seeds, {}, offset)
+
+    def sample_excluding(self, seeds: Dict[str, Tensor], exclude: Dict[tuple, Tensor],
+                         offset: int = 0) -> "SampledSubgraph":
+        """``sample`` without the edges of ``exclude`` = {relation: int64 [2, M]}, global (src, dst) pairs in that
+        relation's own orientation (include/hgin.h A25): no edge of an excluded pair (no copy of a multi-edge) is in the
+        subgraph, at any hop; a row's fanout is drawn from what is left of it.  A relation without an entry is sampled by
+        the A22 entry points; an empty dict (or only empty entries) returns exactly what ``sample`` returns.  The keys
+        dst * 2^32 + src are sorted on the device; the pairs' range check joins the seeds' one host read."""
+        what = "NeighborSampler.sample_excluding"
+        return self._sample(what, seeds, self._check_exclude(exclude, what), offset)
+
+    def _sample(self, what: str, seeds, exclude: Dict[tuple, Tensor], offset) -> "SampledSubgraph":
         from .data import HeteroGraph
-        what = "NeighborSampler.sample"
-        seeds = self._check_seeds(seeds, offset)
+        seeds = self._check_seeds(seeds, offset, exclude, what)
         g = self.graph
-        ops.require_device(*seeds.values(), *g.x.values(), *[g.edge_index[r] for r in self.relations], what=what)
+        ops.require_device(*seeds.values(), *exclude.values(), *g.x.values(),
+                           *[g.edge_index[r] for r in self.relations], what=what)
         dev = self._device()
         for ids in seeds.values():
             if ids.device != dev:
                 raise ValueError(f"{what}: seeds are on {ids.device}, the graph on {dev}")
+        for r, e in exclude.items():
+            if e.device != dev:
+                raise ValueError(f"{what}: the excluded pairs of {r!r} are on {e.device}, the graph on {dev}")
         offset = int(offset)
+        # A25's keys, ascending: destination (the CSR row) in the high word, source in the low one
+        excl = {r: torch.sort((e[1] << 32) | e[0]).values for r, e in exclude.items()}
         csr = {r: ops.relation_graph(g.edge_index[r], self.num_nodes[r[0]], self.num_nodes[r[2]]).csr
                for r in self.relations}
         empty = torch.empty(0, dtype=torch.int64, device=dev)
@@ -238,8 +286,13 @@ class NeighborSampler:
                     size = ctypes.c_size_t(0)
                     _lib.call("hgin_neighbor_sample_workspace_size", n, ctypes.byref(size))
                     ws = ops._workspace(size.value, dev)
-                    _lib.call("hgin_neighbor_sample_offsets", ops._p(csr[r].rowptr), csr[r].n_rows, ops._p(fr), n, f,
-                              ops._p(off), ops._p(ws), size.value, stream)
+                    if r in excl:
+                        _lib.call("hgin_neighbor_sample_offsets_excl", ops._p(csr[r].rowptr), ops._p(csr[r].col),
+                                  csr[r].n_rows, ops._p(fr), n, f, ops._p(excl[r]), int(excl[r].numel()), ops._p(off),
+                                  ops._p(ws), size.value, stream)
+                    else:
+                        _lib.call("hgin_neighbor_sample_offsets", ops._p(csr[r].rowptr), csr[r].n_rows, ops._p(fr), n,
+                                  f, ops._p(off), ops._p(ws), size.value, stream)
                     jobs.append((slot, r, fr, off))
                 if not jobs:
                     break
@@ -254,9 +307,14 @@ class NeighborSampler:
                     src = torch.empty(tot, dtype=torch.int64, device=dev)
                     eid = torch.empty(tot, dtype=torch.int64, device=dev)
                     c = csr[r]
-                    _lib.call("hgin_neighbor_sample", ops._p(c.rowptr), ops._p(c.col), ops._p(c.perm), c.n_rows,
-                              ops._p(fr), n, f, self.seed, offset, slot, ops._p(off), ops._p(src), ops._p(eid), tot,
-                              stream)
+                    if r in excl:
+                        _lib.call("hgin_neighbor_sample_excl", ops._p(c.rowptr), ops._p(c.col), ops._p(c.perm),
+                                  c.n_rows, ops._p(fr), n, f, self.seed, offset, slot, ops._p(excl[r]),
+                                  int(excl[r].numel()), ops._p(off), ops._p(src), ops._p(eid), tot, stream)
+                    else:
+                        _lib.call("hgin_neighbor_sample", ops._p(c.rowptr), ops._p(c.col), ops._p(c.perm), c.n_rows,
+                                  ops._p(fr), n, f, self.seed, offset, slot, ops._p(off), ops._p(src), ops._p(eid),
+                                  tot, stream)
                     new = torch.empty(tot, dtype=torch.int64, device=dev)
                     _lib.call("hgin_neighbor_fresh", ops._p(self._map(r[0], dev)), self.num_nodes[r[0]], ops._p(src),
                               tot, self.num_nodes[r[0]], ops._p(new), stream)

@@ -899,6 +899,52 @@ int hgin_link_lse_bwd_dst_seg_f32(const int64_t* src, int64_t n_query, int64_t n
                                   const float* g, float* g_dst, int64_t ld_gdst, void* ws, size_t ws_bytes,
                                   const int32_t* src_seg, const int32_t* dst_ptr, int64_t n_graphs, void* stream);
 
+/* ---- A25: neighbour sampling with an excluded set (NOT IN REFERENCE; build-defined; added to ABI 16 without a bump:
+ * purely additive, no earlier entry point changes) ----------------------------------------------------------------------
+ * A batch of supervised pairs must not pass messages over its own target edges.  A25 is A22's sampling rule over the
+ * positions of a row that are not excluded, so that the pairs (and their flipped twins in the reverse relation) leave the
+ * sampled neighbourhood of that batch alone; the sampler's graph and its CSRs stay as they are.
+ *
+ * Excluded set of one relation: excl int64 [n_excl], ascending, repeats allowed; key(v, u) = v * 2^32 + u for
+ * destination v (the CSR row that is expanded) and source u, both in [0, 2^31).
+ * Row of frontier node v, d = rowptr[v + 1] - rowptr[v]: position p in [0, d) is excluded iff
+ * key(v, col[rowptr[v] + p]) occurs in excl; every copy of a multi-edge goes (as in A21, a pair's fate is a function of
+ * the pair).  The free positions are q_0 < q_1 < .. < q_{d' - 1}.  Picks:
+ *   f == -1 or d' <= f: every free position; no Philox word is consumed.
+ *   otherwise A22's Floyd steps over [0, d'): for i = 0 .. f - 1
+ *     J = d' - f + i
+ *     w_i = the same word as A22: counter {(uint32)v, offset, 2, (uint32)(r_slot * 64 + (i >> 2))}, key = seed
+ *     t = hi32((uint64)w_i * (J + 1));  pick t if it has not been picked yet, else pick J.
+ *   A picked rank t means CSR position q_t.  Emission is in ascending CSR position, col / perm as in A22.
+ * A row with no excluded position gives A22's picks bit for bit.  A key that names no edge, or a row that is not in the
+ * frontier, has no effect.  The picks are a pure function of (seed, offset, r_slot, v, the excluded sources of v).
+ *
+ * Entry points (plain launches; no workgroup waits on another; no atomics; the output does not depend on execution
+ * order):
+ *   hgin_neighbor_sample_offsets_excl: off int64 [n_frontier + 1] = the exclusive scan of min(d', f) (d' when f = -1),
+ *     the total in off[n_frontier].  A lane finds its node's key range in excl with two binary searches; a node with an
+ *     empty range reads no row; the wave then sweeps the rows that have one, 64 positions per round (membership: a binary
+ *     search of the position's key inside the node's range; d' = the popcounts of the free-flag ballots).  The scan and
+ *     the tile offsets are A22's launches.  Workspace: hgin_neighbor_sample_workspace_size(n_frontier), as A22; nothing
+ *     is carried from this call to the next one.
+ *   hgin_neighbor_sample_excl: out_src / out_eid under the rule above.  A22's lane groups; the group's lead lane finds
+ *     the key range; a row with an empty range takes A22's path (f positions read).  A row with exclusions is swept by
+ *     the whole wave: once for d', and once more where the popcount prefix of the free-flag ballot is the compaction
+ *     slot (copied rows) or maps the picked ranks to CSR positions (Floyd rows): O(d / 64 * log x_v + f^2 / W) for a row
+ *     with x_v keys, unchanged otherwise.  No per-row list is kept in registers or LDS, so x_v is unbounded.  Every loop
+ *     around a ballot or shuffle runs on wave-uniform values.
+ *   n_excl = 0 (excl may then be NULL) gives the A22 calls' outputs bit for bit.
+ * Status: as A22, plus HGIN_E_ARG before any launch for excl = NULL with n_excl > 0 and n_excl outside [0, 2^31).  The
+ *   offsets call accepts col = NULL for a relation without edges (no row is swept then).  The A22 kernels and entry
+ *   points are unchanged. */
+int hgin_neighbor_sample_offsets_excl(const int32_t* rowptr, const int32_t* col, int64_t n_rows, const int64_t* frontier,
+                                      int64_t n_frontier, int f, const int64_t* excl, int64_t n_excl, int64_t* off,
+                                      void* ws, size_t ws_bytes, void* stream);
+int hgin_neighbor_sample_excl(const int32_t* rowptr, const int32_t* col, const int32_t* perm, int64_t n_rows,
+                              const int64_t* frontier, int64_t n_frontier, int f, uint64_t seed, uint32_t offset,
+                              int64_t r_slot, const int64_t* excl, int64_t n_excl, const int64_t* off, int64_t* out_src,
+                              int64_t* out_eid, int64_t n_out, void* stream);
+
 /* ---- F4 widening: HetroGAT's graph attention (models.py:380-506, PyG 2.0.2 GATConv) ---------------------------
  * x_s / x_d: projected source / destination features [N, H * C] (row stride ld*), edges = the relation after
  * GATConv's self-loop handling, as CSR by destination (rowptr, col) and CSC by source (cptr, cdst, cpos = the CSR

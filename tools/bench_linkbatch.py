@@ -19,6 +19,14 @@ convergence.  There is no CPU fallback: without a HIP device the tool prints the
 
     python tools/bench_linkbatch.py --out profiles/linkbatch/linkbatch_bench.json
     python tools/bench_linkbatch.py --configs cfg1 --batch 64            # a tiny run
+
+``--exclude`` times the batch without its own target edges (include/hgin.h A25) at the same shapes instead, all paths
+alternating in one run: ``hgin.link_neighbor_batch_excl`` against ``hgin.link_neighbor_batch`` on the same tensors,
+both against the only way there was before (``torch.isin`` masks the batch's pairs out of both relations'
+``edge_index``, a fresh ``NeighborSampler`` builds its CSRs on the result), and ``hgin.link_minibatch_step`` with and
+without ``LinkPredictor(exclude_targets=True)``:
+
+    python tools/bench_linkbatch.py --exclude --out profiles/linkexcl/linkexcl_bench.json
 """
 import argparse
 import importlib.util
@@ -205,6 +213,120 @@ def run_shape(torch, shape, repeats, warmup, target_ms, seed=1234):
     return out
 
 
+def _alternate(torch, lp, paths, repeats, warmup, target_ms, label):
+    """{name: stats} of the callables ``paths``, alternating inside every repeat."""
+    for _ in range(warmup):
+        for fn in paths.values():
+            fn(0)
+    torch.cuda.synchronize()
+    inner = {name: lp._inner_for(torch, fn, target_ms) for name, fn in paths.items()}
+    times = {name: [] for name in paths}
+    for _ in range(repeats):
+        for name, fn in paths.items():
+            times[name].append(lp._timed(torch, fn, inner[name], 1))
+    out = {}
+    for name in paths:
+        out[name] = dict(lp._stats(times[name]), inner=inner[name])
+        print(f"{label}: {name}: median {out[name]['median_ms']:.3f} ms [{out[name]['min_ms']:.3f} - "
+              f"{out[name]['max_ms']:.3f}]", file=sys.stderr, flush=True)
+    return out
+
+
+def _beyond(a, b):
+    """a against b: 'faster' / 'slower' when the whole spread of a lies on one side of b's, else 'inside'."""
+    if a["max_ms"] < b["min_ms"]:
+        return "faster"
+    return "slower" if a["min_ms"] > b["max_ms"] else "inside"
+
+
+def run_exclude(torch, shape, repeats, warmup, target_ms, seed=1234):
+    """--exclude: what keeping a batch's own target edges out of its neighbourhood costs (include/hgin.h A25).  The
+    positives are edges of the graph, so every batch has B pairs to exclude in path -> link and B in link -> path."""
+    lp = _tool("bench_linkpred")
+    import hgin
+    from hgin.data import CONFIGS, CONV_RELATIONS, REL_LP, REL_PL, HeteroGraph, synthetic_graph
+    from hgin.linkpred import sample_negative_dst
+    dev = "cuda"
+    cfg = CONFIGS[shape["config"]]
+    B, k, fanouts = shape["B"], shape["k"], shape["fanouts"]
+    graph = synthetic_graph(cfg, seed=0, device=dev)
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    all_pos = graph.edge_index[REL_PL]
+    n_dst = cfg.n_link
+    sampler = hgin.NeighborSampler(graph, fanouts=fanouts, relations=CONV_RELATIONS, seed=seed)
+
+    def batch_of(step):
+        idx = torch.randint(0, all_pos.size(1), (B,), device=dev, generator=gen)
+        pos = all_pos[:, idx].contiguous()
+        neg = sample_negative_dst(B * k, n_dst, seed, step * B * k, dev).view(B, k)
+        return pos, neg
+
+    def plain(step):
+        pos, neg = batch_of(step)
+        return hgin.link_neighbor_batch(sampler, REL_PL, pos, neg, offset=step)
+
+    def excl(step):
+        pos, neg = batch_of(step)
+        return hgin.link_neighbor_batch_excl(sampler, REL_PL, pos, neg, offset=step)
+
+    def rebuild(step):
+        # the only way before A25: mask the batch's pairs out of both relations and build a sampler on what is left
+        pos, neg = batch_of(step)
+        keys = pos[0] * n_dst + pos[1]
+        pl, lp_ = graph.edge_index[REL_PL], graph.edge_index[REL_LP]
+        ei = dict(graph.edge_index)
+        ei[REL_PL] = pl[:, ~torch.isin(pl[0] * n_dst + pl[1], keys)]
+        ei[REL_LP] = lp_[:, ~torch.isin(lp_[1] * n_dst + lp_[0], keys)]
+        fresh = hgin.NeighborSampler(HeteroGraph(graph.x, ei, graph.y, graph.batch), fanouts=fanouts,
+                                     relations=CONV_RELATIONS, seed=seed)
+        return hgin.link_neighbor_batch(fresh, REL_PL, pos, neg, offset=step)
+
+    out = dict(shape)
+    # the three batches of one step agree on what they are: the excluded one holds no target edge, the rebuilt one is
+    # the same subgraph (same rows, same edges; its e_id counts positions of the masked lists)
+    pos, neg = batch_of(1)
+    a = hgin.link_neighbor_batch(sampler, REL_PL, pos, neg, offset=1).sub
+    b = hgin.link_neighbor_batch_excl(sampler, REL_PL, pos, neg, offset=1).sub
+    e = b.graph.edge_index[REL_PL]
+    back = b.n_id["path"][e[0]] * n_dst + b.n_id["link"][e[1]]
+    ea = a.graph.edge_index[REL_PL]
+    held = a.n_id["path"][ea[0]] * n_dst + a.n_id["link"][ea[1]]
+    keys = pos[0] * n_dst + pos[1]
+    out["check"] = {"target_edges_in_plain_batch": int(torch.isin(held, keys).sum()),
+                    "target_edges_in_excluded_batch": int(torch.isin(back, keys).sum()),
+                    "edges_plain": int(sum(v.size(1) for v in a.graph.edge_index.values())),
+                    "edges_excluded": int(sum(v.size(1) for v in b.graph.edge_index.values()))}
+    del a, b
+    case = _alternate(torch, lp, {"plain": plain, "excl": excl, "rebuild": rebuild}, repeats, warmup, target_ms,
+                      f"{cfg.name} batch")
+    case["excl_over_plain"] = case["excl"]["median_ms"] / case["plain"]["median_ms"]
+    case["rebuild_over_excl"] = case["rebuild"]["median_ms"] / case["excl"]["median_ms"]
+    case["excl_vs_plain"] = _beyond(case["excl"], case["plain"])
+    case["excl_vs_rebuild"] = _beyond(case["excl"], case["rebuild"])
+    out["batch"] = case
+
+    torch.manual_seed(1997)
+    model = hgin.HetroGIN(**cfg.model_kwargs({"link": cfg.f_link, "path": cfg.f_path, "node": cfg.f_node})).to(dev)
+    opt = torch.optim.Adam(model.parameters(), lr=1e-3)
+    pred = hgin.LinkPredictor(model, REL_PL, k=k, seed=seed)
+    pred_x = hgin.LinkPredictor(model, REL_PL, k=k, seed=seed, exclude_targets=True)
+
+    def step_plain(step):
+        return hgin.link_minibatch_step(model, opt, sampler, pred, batch_of(step)[0], step)
+
+    def step_excl(step):
+        return hgin.link_minibatch_step(model, opt, sampler, pred_x, batch_of(step)[0], step)
+
+    case = _alternate(torch, lp, {"plain": step_plain, "exclude_targets": step_excl}, repeats, warmup, target_ms,
+                      f"{cfg.name} step")
+    case["excl_over_plain"] = case["exclude_targets"]["median_ms"] / case["plain"]["median_ms"]
+    case["excl_vs_plain"] = _beyond(case["exclude_targets"], case["plain"])
+    out["step"] = case
+    del model, opt, pred, pred_x, sampler, graph
+    torch.cuda.empty_cache()
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--configs", default="cfg2,cfg3")
@@ -214,6 +336,9 @@ def main(argv=None) -> int:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--target-ms", type=float, default=200.0, help="device time of one timed repeat, at least")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--exclude", action="store_true",
+                    help="time link_neighbor_batch_excl / exclude_targets (A25) against the plain batch and against "
+                         "masking the pairs out of the graph and rebuilding the sampler")
     args = ap.parse_args(argv)
     if args.repeats < 5:
         ap.error("--repeats must be at least 5")
@@ -229,10 +354,15 @@ def main(argv=None) -> int:
         return 2
     from hgin import _lib
     _lib.lib()
-    results = [run_shape(torch, s, args.repeats, args.warmup, args.target_ms) for s in shapes]
-    doc = {"tool": "tools/bench_linkbatch.py", "device": torch.cuda.get_device_name(0), "repeats": args.repeats,
+    run = run_exclude if args.exclude else run_shape
+    results = [run(torch, s, args.repeats, args.warmup, args.target_ms) for s in shapes]
+    doc = {"tool": "tools/bench_linkbatch.py" + (" --exclude" if args.exclude else ""),
+           "device": torch.cuda.get_device_name(0), "repeats": args.repeats,
            "warmup": args.warmup, "not_measured": ["HetroGAT subgraphs", "hub-heavy (Zipf) graphs",
                                                    "training to convergence"], "shapes": results}
+    if args.exclude:
+        doc["not_measured"] += ["batches whose pairs are not edges of the graph", "batch_full_loss",
+                                "the accuracy effect of the exclusion"]
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
